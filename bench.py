@@ -1,7 +1,12 @@
 """Benchmark: RGBD keypoint inference throughput (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--precision fp16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--precision fp16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: set-up, a short clock ramp, W warm-up
+steps, K timed steps, the optional --dump-outputs, one JSON line.  --full adds every other leg (px-L2
+against the CPU reference, per-launch timing and rooflines, the parity modes, factors, configs[2],
+configs[4] streaming, the CPU baseline); their keys are null in a plain run's line.
 
 Without a launcher (no WORLD_SIZE in the environment) and N > 1, this process starts the N
 ranks itself -- torchrun as a child process, before anything here touches the GPU (the
@@ -33,17 +38,26 @@ MFMA_FP16_DENSE_PEAK = 2.5e15  # MI355X_MICROARCH.md: ~2.5 PF dense fp16/bf16
 MFMA_FP32_PEAK = 157.3e12      # f32-input MFMA peak (= vector f32 rate)
 HBM_PEAK = 8.0e12
 REPS = 20  # back-to-back launches per timed launch in the per-kernel pass
+RAMP_S = 1.0  # plain run: back-to-back forwards in front of the warm-up that bring the clocks up
+# legs behind --full, and the option that turns each off
+FULL_LEGS = ("no_cpu_baseline", "no_factors", "no_parity", "no_trajset", "no_streaming")
 # parity_mode leg: the peak its roofline fraction is taken against, and what it executes
 PARITY_PEAK = {"fp32": (MFMA_FP32_PEAK, 1, "v_mfma_f32_16x16x4_f32 (exact f32 products), f32 NHWC"),
                "fp16x3": (MFMA_FP16_DENSE_PEAK, 3, "3 v_mfma_f32_16x16x32_f16 products per MAC (x_hi w_hi + x_lo w_hi + "
                                                    "x_hi w_lo) on hi/lo fp16 planes, f32 accumulate")}
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=200)
+    p.add_argument("--steps", type=int, default=200, help="timed steps (>= 1)")
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline figure: px-L2 against the CPU reference, per-launch "
+                        "timing and rooflines, parity modes, factors, configs[2], configs[4] streaming, CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write the keypoints of the last timed step to DIR/keypoints.npy "
+                        "(float32, (batch, 16); rank r > 0 writes keypoints_rank<r>.npy)")
     p.add_argument("--batch", type=int, default=64)
     p.add_argument("--precision", default="fp16", choices=["fp16", "fp32"])
     p.add_argument("--parity-precision", default="fp16x3", choices=["fp16x3", "fp32"],
@@ -63,10 +77,16 @@ def parse():
     p.add_argument("--launcher-check", action="store_true",
                    help="CPU-only rehearsal of the N-rank launch: every rank joins a gloo group, checks its size "
                         "and rank 0 prints the ranks that joined (no GPU work)")
-    return p.parse_args()
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if not args.full:
+        for leg in FULL_LEGS:
+            setattr(args, leg, True)
+    return args
 
 
-def launch_ranks(args) -> int:
+def launch_ranks(args, argv) -> int:
     """`bench.py --gpus N` with no launcher around it: run the same command line as N ranks
     under torchrun (a child process; this parent never initialises HIP, so no GPU state is
     inherited or exec'd over) and return its exit status."""
@@ -74,7 +94,7 @@ def launch_ranks(args) -> int:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     return subprocess.call(cmd, env=env)
 
@@ -96,8 +116,9 @@ def launcher_check(args, world, rank):
     dist.destroy_process_group()
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else argv
+    args = parse(argv)
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -106,7 +127,7 @@ def main():
     from perseus_amd.detector import KeypointCNN
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        sys.exit(launch_ranks(args))  # before any GPU call in this process
+        sys.exit(launch_ranks(args, argv))  # before any GPU call in this process
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -135,15 +156,18 @@ def main():
     kp = torch.empty((args.steps, B, 16), dtype=torch.float32, device=dev)
     # CPU-side reference for the accuracy legs, computed before any GPU work so that the
     # GPU legs below run back to back
-    yref = px_reference(state, x_host) if rank == 0 else None
+    yref = px_reference(state, x_host) if args.full and rank == 0 else None
 
-    # ---- measurement legs (untimed for `value`).  They run BEFORE the timed loop: the
+    # ---- measurement legs of --full (untimed for `value`).  They run BEFORE the timed loop: the
     # GPU comes out of them at its sustained clock, so the K-step window measures the
     # steady state even when K is small (the first ~8 ms of load after an
     # idle period run ~15 % slower while the clocks ramp; with only W warm-up forwards in
-    # front, a 20-step window would average that ramp in).
+    # front, a 20-step window would average that ramp in).  A plain run has no legs in front,
+    # so it runs RAMP_S seconds of the same forward instead: `value` is the steady state either way.
     with torch.no_grad():
-        px = px_error(model, x, yref) if rank == 0 else None
+        if not args.full:
+            clock_ramp(model, x, dev)
+        px = px_error(model, x, yref) if args.full and rank == 0 else None
         # configs[4] first: its 30 Hz pacing leaves the GPU mostly idle, the legs after it
         # bring the clocks back up before the timed loop
         stream = None if (args.no_streaming or rank != 0) else streaming_leg(model, dev, args.stream_ticks,
@@ -151,7 +175,7 @@ def main():
         # per-launch device time on the forward's stream: each launch of the forward issued
         # REPS times back to back between two HIP events (pa_detector_time_launch), median
         # over passes; no per-launch event gaps, so it agrees with rocprofv3 kernel-trace.
-        n_launch = len(model.profile(x)[0])
+        n_launch = len(model.profile(x)[0]) if args.full else 0
         per_launch = []
         for idx in range(n_launch):
             v = [model.time_launch(x, idx, REPS) for _ in range(args.profile_passes)]
@@ -183,6 +207,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, kp[args.steps - 1], rank)
 
     frames = world * B * args.steps
     value = frames / elapsed
@@ -190,8 +216,8 @@ def main():
 
     line = None
     if rank == 0:
-        roof = roofline(per_launch, B, args.precision)
-        per_kernel = per_kernel_rooflines(per_launch, B, args.precision)
+        roof = roofline(per_launch, B, args.precision) if args.full else None
+        per_kernel = per_kernel_rooflines(per_launch, B, args.precision) if args.full else None
         # rank 0 at every world size, after the timed region (the other ranks wait at the
         # closing barrier): the driver's N = 1..8 lines each carry the CPU baseline
         cpu = None if args.no_cpu_baseline else cpu_baseline(state, x_host)
@@ -208,6 +234,7 @@ def main():
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": args.precision,
+            "full": args.full,
             "data": "synthetic (seeded RGBD frames + seeded ResNet-18 weights; no dataset/checkpoint offline)",
             "config": {"workload": "keypointcnn_rgbd256_b64_forward", "per_gpu_batch": B, "global_batch": B * world,
                        "H": 256, "W": 256, "channels": 4, "precision": args.precision,
@@ -235,6 +262,30 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return line
+
+
+def clock_ramp(model, x, dev, seconds=RAMP_S):
+    """Back-to-back forwards for `seconds` of wall clock (untimed for `value`): after an idle period
+    the first forwards run at a lower clock, and a short timed window would average that ramp in."""
+    import torch
+
+    t_end = time.perf_counter() + seconds
+    while time.perf_counter() < t_end:
+        for _ in range(50):
+            model(x)
+        torch.cuda.synchronize(dev)
+
+
+def dump_outputs(out_dir, keypoints, rank):
+    """--dump-outputs: what forward(x, out=...) handed back in the last timed step, the (batch, 16)
+    float32 keypoints of this rank's frames, as DIR/keypoints.npy (rank r > 0: keypoints_rank<r>.npy).
+    Weights and frames come from --seed, so two builds run with the same arguments compare array
+    for array."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    name = "keypoints.npy" if rank == 0 else f"keypoints_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), keypoints.float().cpu().numpy())
 
 
 def bench_variants(m, env="PERSEUS_AMD_BENCH_VARIANTS"):

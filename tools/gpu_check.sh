@@ -5,8 +5,9 @@
 #
 #   test            python -m pytest tests -m gpu  ($PYTEST_ARGS, e.g. "-k streaming")
 #   smoke           __graft_entry__.smoke()
-#   bench           python bench.py $BENCH_ARGS            -> bench.jsonl (default: the full bench)
-#   driver          python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's own command)
+#   bench           python bench.py --full $BENCH_ARGS     -> bench.jsonl (every leg of the bench)
+#   driver          python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's own command: a plain run,
+#                   the headline figure alone)
 #   ab:L,L:V,V      interleaved per-launch A/B in one process (tools/layer_ab.py), layers L, variants V
 #                   ($AB_ROUNDS rounds, $AB_ARGS extra, e.g. "--precision fp16x3")
 #   fwdab:L:V[,..]  interleaved whole-forward A/B (tools/head_ab.py --ab L:V ...)
@@ -49,7 +50,7 @@ step() {
       (cd $R && timeout -k 10 300 $PY -c "import __graft_entry__ as g; g.smoke()") > $O/smoke.log 2>&1
       local rc=$?; tail -4 $O/smoke.log; return $rc ;;
     bench)
-      (cd $R && timeout -k 10 ${BENCH_TIMEOUT:-500} $PY bench.py ${BENCH_ARGS}) > $O/bench.jsonl 2>$O/bench.err
+      (cd $R && timeout -k 10 ${BENCH_TIMEOUT:-500} $PY bench.py --full ${BENCH_ARGS}) > $O/bench.jsonl 2>$O/bench.err
       local rc=$?; tail -c 600 $O/bench.jsonl; return $rc ;;
     driver)
       (cd $R && timeout -k 10 500 $PY bench.py --gpus 1 --steps 20 --warmup 5) > $O/bench_driver_cmd.jsonl \
@@ -73,15 +74,15 @@ step() {
       local vs=${s#benchab:}; local ev=PERSEUS_AMD_BENCH_VARIANTS
       if [[ $s == benchabx3:* ]]; then vs=${s#benchabx3:}; ev=PERSEUS_AMD_BENCH_VARIANTS_PARITY; fi
       for k in $(seq ${BENCHAB_PAIRS:-2}); do
-        (cd $R && timeout -k 10 400 $PY bench.py --gpus 1 --steps 20 --warmup 5 --no-streaming) 2>>$O/benchab.err | \
+        (cd $R && timeout -k 10 400 $PY bench.py --full --gpus 1 --steps 20 --warmup 5 --no-streaming) 2>>$O/benchab.err | \
           sed 's/^/{"ab": "shipped", "line": /; s/$/}/' >> $O/benchab.jsonl || return 1
-        (cd $R && env $ev=$vs timeout -k 10 400 $PY bench.py --gpus 1 --steps 20 --warmup 5 \
+        (cd $R && env $ev=$vs timeout -k 10 400 $PY bench.py --full --gpus 1 --steps 20 --warmup 5 \
           --no-streaming) 2>>$O/benchab.err | sed "s/^/{\"ab\": \"$vs\", \"line\": /; s/\$/}/" >> $O/benchab.jsonl || return 1
         echo "pair $k done"
       done ;;
     profile)
       (cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_kt -o kt -- \
-        $PY $R/bench.py ${BENCH_ARGS}) > $O/bench.log 2>&1 && echo bench_kt_ok && \
+        $PY $R/bench.py --full ${BENCH_ARGS}) > $O/bench.log 2>&1 && echo bench_kt_ok && \
       (cd /tmp && timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d $O/fwd_kt -o kt -- \
         $PY $R/tools/pmc_forward.py --out $O ${FWD_ARGS}) > $O/fwd_kt.log 2>&1 && echo fwd_kt_ok && \
       (cd /tmp && timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/x3_kt -o kt -- \

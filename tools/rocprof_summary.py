@@ -3,7 +3,7 @@
     python tools/rocprof_summary.py --dir gpurun_out/r01 --tag r01
 
 Inputs under --dir (rocprofv3 csv):
-  bench_kt/**/kt_kernel_stats.csv   kernel-trace --stats of `python bench.py ...`
+  bench_kt/**/kt_kernel_stats.csv   kernel-trace --stats of `python bench.py --full ...`
   fwd_kt/**/kt_kernel_trace.csv     kernel trace of tools/pmc_forward.py (plain forwards)
   fetch/**/p_counter_collection.csv --pmc FETCH_SIZE pass (same driver)
   write/**/p_counter_collection.csv --pmc WRITE_SIZE pass (same driver)
@@ -120,7 +120,7 @@ def main():
     stats = find(os.path.join(a.dir, "bench_kt"), "*kernel_stats.csv")
     if stats:
         shutil.copy(stats, os.path.join(out, f"{a.tag}_kernel_stats.csv"))
-        lines += ["## kernel-trace --stats of the bench command (`python bench.py`)", "",
+        lines += ["## kernel-trace --stats of the bench command (`python bench.py --full`)", "",
                   "| kernel symbol | launch(es) | calls | avg us | % |", "|---|---|---|---|---|"]
         for r in csv.DictReader(open(stats)):
             nm = ",".join(sorted(sym_names.get(r["Name"], []))) or "-"

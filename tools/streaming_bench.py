@@ -1,7 +1,7 @@
 """Config 4: 3 x 720p RGBD cameras at 30 Hz, end-to-end keypoint and pose latency on 1 GPU.
 
-The measurement is bench.py's `streaming_leg` (the same numbers appear in every bench
-line as "streaming"): per tick, stage the 3 frames (host -> pinned, centre crop), one
+The measurement is bench.py's `streaming_leg` (the same numbers appear in every
+`bench.py --full` line as "streaming"): per tick, stage the 3 frames (host -> pinned, centre crop), one
 hipGraph replay (H2D, preprocess, B=3 forward, denormalize, D2H; with the pose stage
 also window advance, factor linearize, GN step, retract, D2H poses), wait.  Prints one
 JSON line.
