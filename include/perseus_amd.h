@@ -59,7 +59,8 @@ void pa_detector_destroy(pa_detector* d);
 
 /* Pre-size the activation workspace for batches up to max_batch (clamped to the
  * 1,024-frame chunk a forward runs in), and for 4-channel models in fp16x3 / fp32 also
- * forward_rgbd's f32 input staging (a later set_precision keeps the reservation).
+ * forward_rgbd's f32 input staging, for 3-channel models forward_rgb's (a later
+ * set_precision keeps the reservation).
  * Without it, allocation is done lazily by the first call of a larger batch, which
  * frees the smaller buffer: capture a graph only after reserve() (or after an eager
  * call of the same batch), and reserve the largest batch any graph will replay. */
@@ -99,6 +100,34 @@ int pa_detector_forward_rgbd(pa_detector* d, const uint8_t* rgb_dev, const float
  * tick's detector call (one launch fewer per tick). */
 int pa_detector_forward_rgbd_px(pa_detector* d, const uint8_t* rgb_dev, const float* depth_dev, int B, int Hs, int Ws,
                                 int bgr, float near_m, float far_m, float* y_dev, float* px_dev, void* stream);
+
+/* RGB-only frames -> keypoints, for 3-channel models (scripts/streaming.py:104,112-128 with an
+ * RGB model; perseus/detector/validate_real.py:62-74): uint8 HWC [B][Hs][Ws][3], RGB byte
+ * order (bgr != 0: BGR).  resize_short = 0: x = u8 / 255 at the centre 256x256 window (origin
+ * Hs/2 - 128, Ws/2 - 128; needs Hs, Ws >= 256).  resize_short = S >= 256: u8 / 255, bilinear
+ * resize (align_corners false, no antialiasing: torch.nn.functional.interpolate's f32
+ * arithmetic) so that the short side is S (kornia resize, side = "short"), then the centre
+ * 256x256 window of the resized image (kornia center_crop); any Hs, Ws >= 1.  Other values
+ * of resize_short, a model that is not 3-channel and null pointers return PA_EINVAL before
+ * any launch; B = 0 is a no-op.  fp16: applied inside the stem's row loads (the f32 input is
+ * never written); fp16x3 / fp32: pa_preprocess_rgb's kernel into the handle's f32 staging
+ * (sized by pa_detector_reserve, else by the first call of a larger batch), then the forward.
+ * Output bit-identical to pa_preprocess_rgb + pa_detector_forward. */
+int pa_detector_forward_rgb(pa_detector* d, const uint8_t* rgb_dev, int B, int Hs, int Ws, int bgr,
+                            int resize_short, float* y_dev, void* stream);
+/* The same, the head also writing the pixel coordinates px (B, n_kp, 2) as
+ * pa_detector_forward_rgbd_px does: the RGB streaming tick's detector call. */
+int pa_detector_forward_rgb_px(pa_detector* d, const uint8_t* rgb_dev, int B, int Hs, int Ws, int bgr,
+                               int resize_short, float* y_dev, float* px_dev, void* stream);
+/* pa_detector_profile of pa_detector_forward_rgb (same outputs; diagnostics only). */
+int pa_detector_profile_rgb(pa_detector* d, const uint8_t* rgb_dev, int B, int Hs, int Ws, int bgr,
+                            int resize_short, float* y_dev, void* stream, float* ms_out, const char** names_out,
+                            int max_n);
+/* The arithmetic of pa_detector_forward_rgb's input alone: x (B,3,H,W) f32 NCHW on the device
+ * (H = W = 256 only). */
+int pa_preprocess_rgb(const uint8_t* rgb_dev, int B, int Hs, int Ws, int bgr, int resize_short, int H, int W,
+                      float* x_dev, void* stream);
+
 /* The device address of a mapped pinned host buffer (hipHostGetDevicePointer): forward_rgbd
  * may read the camera frames straight from host memory over PCIe (zero-copy), so a tick
  * needs no H2D copy before the stem (StreamingPipeline(zero_copy=True)). */

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "conv.h"
+#include "rgb_src.h"
 
 namespace pa {
 
@@ -695,6 +696,69 @@ int launch_preprocess(const uint8_t* rgb, const float* depth, int B, int Hs, int
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(preprocess_kernel, dim3((unsigned)blocks), dim3(256), 0, s, rgb, depth, B, Hs, Ws, bgr, near_m,
                      far_m, H, W, x);
+  PA_LAUNCH_CHECK();
+  return PA_OK;
+}
+
+// RGB-only frames (rgb_src.h): uint8 HWC, centre crop or bilinear resize + centre crop ->
+// f32 NCHW (B,3,256,256).  The bit-exact reference form of the fp16 stem's fused RGB source,
+// and the fp16x3 / fp32 path into the handle's staging.  One thread per output pixel.
+__global__ void preprocess_rgb_kernel(RgbSrc src, int B, float* __restrict__ x) {
+  const long total = (long)B * 256 * 256;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int wc = (int)(i & 255), hr = (int)((i >> 8) & 255), n = (int)(i >> 16);
+    const uint8_t* f = src.rgb + (size_t)n * src.Hs * src.Ws * 3;
+    float* xo = x + ((size_t)n * 3 * 256 + hr) * 256 + wc;
+    if (src.resize) {
+      const RgbTap ty = rgb_tap(src.r0 + hr, src.Hs, src.sy), tx = rgb_tap(src.c0 + wc, src.Ws, src.sx);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) xo[(size_t)c * 256 * 256] = rgb_resized(f, src.Ws, src.bgr ? 2 - c : c, ty, tx);
+    } else {
+      const uint8_t* px = f + ((size_t)(src.r0 + hr) * src.Ws + src.c0 + wc) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) xo[(size_t)c * 256 * 256] = rgb_unit(px[src.bgr ? 2 - c : c]);
+    }
+  }
+}
+
+void real_image_size(int Hs, int Ws, int S, int* Hr, int* Wr) {
+  const double ar = (double)Ws / Hs;
+  if (ar < 1.0) {
+    *Hr = (int)(S / ar);
+    *Wr = S;
+  } else {
+    *Hr = S;
+    *Wr = (int)(S * ar);
+  }
+}
+
+int make_rgb_src(const uint8_t* rgb, int Hs, int Ws, int bgr, int resize_short, RgbSrc* out) {
+  PA_CHECK(rgb, "rgb: null frame pointer");
+  PA_CHECK(resize_short == 0 || resize_short >= 256, "rgb: resize_short %d is neither 0 (no resize) nor >= 256",
+           resize_short);
+  PA_CHECK(Hs >= 1 && Ws >= 1, "rgb: source %dx%d", Hs, Ws);
+  RgbSrc r{rgb, Hs, Ws, bgr ? 1 : 0, resize_short != 0, 0, 0, 1.f, 1.f};
+  int Hr = Hs, Wr = Ws;
+  if (resize_short) {
+    const double lo = Hs < Ws ? Hs : Ws, hi = Hs < Ws ? Ws : Hs;
+    PA_CHECK(resize_short * (hi / lo) < 1073741824.0, "rgb: %dx%d resized to a short side of %d is too large", Hs, Ws,
+             resize_short);
+    real_image_size(Hs, Ws, resize_short, &Hr, &Wr);
+    r.sy = (float)Hs / (float)Hr;
+    r.sx = (float)Ws / (float)Wr;
+  }
+  PA_CHECK(Hr >= 256 && Wr >= 256, "rgb: source %dx%d smaller than 256x256 (no resize requested)", Hs, Ws);
+  r.r0 = Hr / 2 - 128;
+  r.c0 = Wr / 2 - 128;
+  *out = r;
+  return PA_OK;
+}
+
+int launch_preprocess_rgb(const RgbSrc& src, int B, float* x, hipStream_t s) {
+  if (B <= 0) return PA_OK;
+  long blocks = ((long)B * 256 * 256 + 255) / 256;
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(preprocess_rgb_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, B, x);
   PA_LAUNCH_CHECK();
   return PA_OK;
 }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "conv.h"
+#include "rgb_src.h"
 
 namespace pa {
 
@@ -442,7 +443,7 @@ struct Prof {
 // the caller's whole batch (a chunk of a larger batch never switches to it)
 template <typename T>
 static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_t s, Prof* prof, bool small,
-                     const RgbdSrc* rgbd = nullptr, float* px = nullptr) {
+                     const RgbdSrc* rgbd = nullptr, float* px = nullptr, const RgbSrc* rgb = nullptr) {
   const T* wts = std::is_same<T, float>::value ? (const T*)d->w32 : (const T*)d->w16;
   T* S = reinterpret_cast<T*>(d->ws);
   const size_t stem_el = stem_elems(B, d->prec);
@@ -464,6 +465,8 @@ static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_
     // fused conv7x7 + BN + ReLU + maxpool: the 128x128 map stays on chip
     if (rgbd)  // camera frames straight into the stem (preprocess fused into its row loads)
       PA_RUN(launch_stem_pool_rgbd(*rgbd, B, wts + st.w_off, d->bias + st.b_off, X, s), "stem_rgbd_conv7x7_pool");
+    else if (rgb)  // RGB-only frames (3-channel models): crop or resize + crop in the row loads
+      PA_RUN(launch_stem_pool_rgb(*rgb, B, wts + st.w_off, d->bias + st.b_off, X, s), "stem_rgb_conv7x7_pool");
     else
       PA_RUN(launch_stem_pool_fp16(x, B, d->in_ch, wts + st.w_off, d->bias + st.b_off, X, s), "stem_conv7x7_pool");
   } else {
@@ -782,7 +785,8 @@ static int forward(pa_detector* d, const float* x, int B, float* y, hipStream_t 
 }
 
 // the f32 (B, 4, 256, 256) input of the non-fused RGBD path (fp16x3 / fp32), grown outside
-// any captured graph (the first call of a given batch size allocates)
+// any captured graph (the first call of a given batch size allocates); forward_rgb's
+// (B, 3, 256, 256) input uses the same buffer
 static int ensure_xin(pa_detector* d, int B) {
   if (B <= d->xin_cap) return PA_OK;
   if (d->xin) PA_HIP(hipFree(d->xin));
@@ -832,9 +836,97 @@ static int forward_rgbd(pa_detector* d, const RgbdSrc& src, int B, float* y, hip
   return PA_OK;
 }
 
+// RGB-only frames -> keypoints (3-channel models; rgb_src.h).  fp16: crop / resize + crop fused
+// into the stem's row loads; fp16x3 / fp32: preprocess_rgb_kernel into the handle's f32 staging,
+// then the forward.  Every argument is checked before the first launch.
+static int forward_rgb(pa_detector* d, const uint8_t* rgb, int B, int Hs, int Ws, int bgr, int resize_short, float* y,
+                       hipStream_t s, float* px = nullptr, Prof* prof = nullptr) {
+  PA_CHECK(d, "null detector");
+  PA_CHECK(B >= 0, "batch %d", B);
+  if (B == 0) return PA_OK;
+  PA_CHECK(rgb && y, "null input/output pointer");
+  PA_CHECK(d->in_ch == 3, "forward_rgb: needs a 3-channel (RGB) model, have %d", d->in_ch);
+  RgbSrc src;
+  PA_TRY(make_rgb_src(rgb, Hs, Ws, bgr, resize_short, &src));
+  PA_TRY(ensure_ws(d, B < kChunk ? B : kChunk));
+  const bool fused = d->prec == PA_PREC_FP16;
+  if (!fused) PA_TRY(ensure_xin(d, B < kChunk ? B : kChunk));
+  HandleScope hs(d);
+  const bool small = small_mode(d, B);
+  const size_t frame = (size_t)Hs * Ws * 3;
+  for (int off = 0; off < B; off += kChunk) {
+    const int nb = B - off < kChunk ? B - off : kChunk;
+    RgbSrc c = src;
+    c.rgb = rgb + off * frame;
+    float* yc = y + off * 2 * (size_t)d->n_kp;
+    float* pc = px ? px + off * 2 * (size_t)d->n_kp : nullptr;
+    if (fused) {
+      PA_TRY(forward_t<_Float16>(d, nullptr, nb, yc, s, prof, small, nullptr, pc, &c));
+    } else {
+      if (prof) prof->mark("start");
+      PA_TRY(launch_preprocess_rgb(c, nb, d->xin, s));
+      if (prof) prof->mark("preprocess_rgb");
+      PA_TRY(forward_chunk(d, d->xin, nb, yc, s, prof, small, pc));
+    }
+  }
+  return PA_OK;
+}
+
+// per-kernel durations from a profiled call's events (pa_detector_profile's output)
+static int prof_collect(Prof& p, int rc, float* ms_out, const char** names_out, int max_n) {
+  if (rc == PA_OK && hipStreamSynchronize(p.s) != hipSuccess) {
+    set_error("profile: stream sync failed");
+    rc = PA_EHIP;
+  }
+  int n = 0;
+  if (rc == PA_OK) {
+    for (size_t i = 1; i < p.ev.size() && n < max_n; ++i) {
+      if (!strcmp(p.names[i], "start")) continue;  // (the forward's own first mark, after the preprocess)
+      float ms = 0.f;
+      hipEventElapsedTime(&ms, p.ev[i - 1], p.ev[i]);
+      if (ms_out) ms_out[n] = ms;
+      if (names_out) names_out[n] = p.names[i];
+      ++n;
+    }
+  }
+  for (hipEvent_t e : p.ev) hipEventDestroy(e);
+  return rc == PA_OK ? n : rc;
+}
+
 }  // namespace pa
 
 extern "C" {
+
+int pa_preprocess_rgb(const uint8_t* rgb_dev, int B, int Hs, int Ws, int bgr, int resize_short, int H, int W,
+                      float* x_dev, void* stream) {
+  PA_CHECK(B >= 0, "batch %d", B);
+  if (B == 0) return PA_OK;
+  PA_CHECK(rgb_dev && x_dev, "null pointer");
+  PA_CHECK(H == 256 && W == 256, "preprocess_rgb: only 256x256 outputs are supported (got %dx%d)", H, W);
+  pa::RgbSrc src;
+  PA_TRY(pa::make_rgb_src(rgb_dev, Hs, Ws, bgr, resize_short, &src));
+  return pa::launch_preprocess_rgb(src, B, x_dev, (hipStream_t)stream);
+}
+
+int pa_detector_forward_rgb(pa_detector* d, const uint8_t* rgb_dev, int B, int Hs, int Ws, int bgr, int resize_short,
+                            float* y_dev, void* stream) {
+  return pa::forward_rgb(d, rgb_dev, B, Hs, Ws, bgr, resize_short, y_dev, (hipStream_t)stream);
+}
+
+int pa_detector_forward_rgb_px(pa_detector* d, const uint8_t* rgb_dev, int B, int Hs, int Ws, int bgr,
+                               int resize_short, float* y_dev, float* px_dev, void* stream) {
+  PA_CHECK(px_dev, "forward_rgb_px: null pixel output");
+  return pa::forward_rgb(d, rgb_dev, B, Hs, Ws, bgr, resize_short, y_dev, (hipStream_t)stream, px_dev);
+}
+
+int pa_detector_profile_rgb(pa_detector* d, const uint8_t* rgb_dev, int B, int Hs, int Ws, int bgr, int resize_short,
+                            float* y_dev, void* stream, float* ms_out, const char** names_out, int max_n) {
+  PA_CHECK(B <= pa::kChunk, "profile: batch %d above the %d-frame chunk (profile one chunk)", B, pa::kChunk);
+  pa::Prof p;
+  p.s = (hipStream_t)stream;
+  const int rc = pa::forward_rgb(d, rgb_dev, B, Hs, Ws, bgr, resize_short, y_dev, p.s, nullptr, &p);
+  return pa::prof_collect(p, rc, ms_out, names_out, max_n);
+}
 
 int pa_detector_forward_rgbd(pa_detector* d, const uint8_t* rgb_dev, const float* depth_dev, int B, int Hs, int Ws,
                              int bgr, float near_m, float far_m, float* y_dev, void* stream) {
@@ -925,7 +1017,8 @@ int pa_detector_reserve(pa_detector* d, int max_batch) {
   // forward_rgbd's f32 staging (fp16x3 / fp32 on a 4-channel model): reserved here too, so
   // that a graph captured after reserve() never allocates, and never keeps a pointer that a
   // later larger call frees
-  if (d->in_ch == 4 && d->prec != PA_PREC_FP16) PA_TRY(pa::ensure_xin(d, n));
+  // (3-channel models: forward_rgb's staging, the same buffer)
+  if (d->in_ch >= 3 && d->prec != PA_PREC_FP16) PA_TRY(pa::ensure_xin(d, n));
   d->reserved = n > d->reserved ? n : d->reserved;
   return PA_OK;
 }
@@ -959,8 +1052,8 @@ int pa_detector_set_precision(pa_detector* d, int precision) {
     while (bcap < pa::kChunk && pa::ws_need(bcap + 1, d->prec) <= old) ++bcap;
     d->prec = precision;
     if (bcap > 0) PA_TRY(pa::ensure_ws(d, bcap));
-    // a reservation covers forward_rgbd's staging in the new precision too
-    if (d->reserved > 0 && d->in_ch == 4 && precision != PA_PREC_FP16) PA_TRY(pa::ensure_xin(d, d->reserved));
+    // a reservation covers forward_rgbd's / forward_rgb's staging in the new precision too
+    if (d->reserved > 0 && d->in_ch >= 3 && precision != PA_PREC_FP16) PA_TRY(pa::ensure_xin(d, d->reserved));
   }
   return PA_OK;
 }

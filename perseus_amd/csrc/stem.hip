@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "conv_gx.h"
+#include "rgb_src.h"
 
 namespace pa {
 
@@ -296,10 +297,33 @@ __global__ __launch_bounds__(512) void stem_pool3_fp16(const float* __restrict__
 // behind them barely overlapped the pipe)
 // (BR and IL shipped this round: 27.3 vs 28.1 us per B = 64 launch, bit-identical, profiles/r05zl_stem_ab.log;
 // variant 0:34 is the previous form)
-template <int PBT, int D, bool PRE = false, int DBG = 0, bool XM = false, bool BR = true, bool IL = true>
+// PRE: the source of the input rows.  SRC_F32 the f32 NCHW tensor x; SRC_RGBD the camera frames
+// (RgbdSrc, preprocess_kernel's arithmetic); SRC_RGB / SRC_RGB_RESIZE RGB-only uint8 frames
+// (RgbSrc, rgb_src.h: preprocess_rgb_kernel's arithmetic, centre crop / bilinear resize + crop;
+// channel 3 is zero and Cin = 3 masks it).  A template parameter, so each source is its own
+// instantiation and the others' code does not change.
+// (plain ints and a named trait: the kernel's mangled name must be the same in the host and the
+// device pass, which number an unnamed enum differently)
+constexpr int SRC_F32 = 0, SRC_RGBD = 1, SRC_RGB = 2, SRC_RGB_RESIZE = 3;
+template <int PRE>
+struct StemSrc {
+  using type = RgbdSrc;
+};
+template <>
+struct StemSrc<SRC_RGB> {
+  using type = RgbSrc;
+};
+template <>
+struct StemSrc<SRC_RGB_RESIZE> {
+  using type = RgbSrc;
+};
+template <int PRE>
+using stem_src_t = typename StemSrc<PRE>::type;
+
+template <int PBT, int D, int PRE = SRC_F32, int DBG = 0, bool XM = false, bool BR = true, bool IL = true>
 __global__ __launch_bounds__(512) void stem_role_fp16(const float* __restrict__ x, int B, int Cin,
                                                       const _Float16* __restrict__ w, const float* __restrict__ bias,
-                                                      _Float16* __restrict__ out, RgbdSrc src,
+                                                      _Float16* __restrict__ out, stem_src_t<PRE> src,
                                                       unsigned long long* trace) {
   auto stamp = [&](int slot) __attribute__((always_inline)) {
     if constexpr (DBG == 4) {
@@ -340,7 +364,52 @@ __global__ __launch_bounds__(512) void stem_role_fp16(const float* __restrict__ 
   const int lr = mt >> 6, lcg = mt & 63;
   auto load_rows = [&](int hi0, float4* v) __attribute__((always_inline)) {
     const int hi = min(max(hi0 + lr, 0), 255);
-    if constexpr (PRE) {
+    if constexpr (PRE == SRC_RGB) {
+      // the 4 pixels' 12 bytes as 3 dwords when the row start is 4-byte aligned (odd-width
+      // sources are not), else byte loads
+      uint8_t px[12];
+      const uint8_t* p8 = src.rgb + (((size_t)n * src.Hs + hi + src.r0) * src.Ws + src.c0 + lcg * 4) * 3;
+      if ((((uintptr_t)p8) & 3) == 0) {
+        const uint32_t* p32 = reinterpret_cast<const uint32_t*>(p8);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const uint32_t wv = p32[j];
+#pragma unroll
+          for (int b = 0; b < 4; ++b) px[4 * j + b] = (uint8_t)(wv >> (8 * b));
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 12; ++j) px[j] = p8[j];
+      }
+      float a[3][4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float c0 = rgb_unit(px[3 * k]), c2 = rgb_unit(px[3 * k + 2]);  // constant indices: no scratch array
+        a[0][k] = src.bgr ? c2 : c0;
+        a[1][k] = rgb_unit(px[3 * k + 1]);
+        a[2][k] = src.bgr ? c0 : c2;
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = float4{a[c][0], a[c][1], a[c][2], a[c][3]};
+      v[3] = float4{0.f, 0.f, 0.f, 0.f};
+    } else if constexpr (PRE == SRC_RGB_RESIZE) {
+      // the four bilinear taps of each pixel and channel (tap indices are clamped to the
+      // source, so every read is inside the frame)
+      const uint8_t* f = src.rgb + (size_t)n * src.Hs * src.Ws * 3;
+      const RgbTap ty = rgb_tap(src.r0 + hi, src.Hs, src.sy);
+      const int s0 = src.bgr ? 2 : 0;
+      float a[3][4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const RgbTap tx = rgb_tap(src.c0 + lcg * 4 + k, src.Ws, src.sx);
+        a[0][k] = rgb_resized(f, src.Ws, s0, ty, tx);
+        a[1][k] = rgb_resized(f, src.Ws, 1, ty, tx);
+        a[2][k] = rgb_resized(f, src.Ws, 2 - s0, ty, tx);
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = float4{a[c][0], a[c][1], a[c][2], a[c][3]};
+      v[3] = float4{0.f, 0.f, 0.f, 0.f};
+    } else if constexpr (PRE == SRC_RGBD) {
       const int r0 = src.Hs / 2 - 128, c0 = src.Ws / 2 - 128;
       const size_t row = ((size_t)n * src.Hs + hi + r0) * src.Ws + c0 + lcg * 4;
       // the 4 pixels' 12 bytes as 3 dwords and their depths as one float4 when aligned (the
@@ -589,9 +658,9 @@ __global__ __launch_bounds__(512) void stem_role_fp16(const float* __restrict__ 
   }
 }
 
-template <int PBT, int D, bool PRE = false, int DBG = 0, bool XM = false, bool BR = true, bool IL = true>
+template <int PBT, int D, int PRE = SRC_F32, int DBG = 0, bool XM = false, bool BR = true, bool IL = true>
 static int run_stem4(const float* x, int B, int Cin, const _Float16* w, const float* bias, _Float16* out, hipStream_t s,
-                     RgbdSrc src = RgbdSrc{}, unsigned long long* trace = nullptr) {
+                     stem_src_t<PRE> src = stem_src_t<PRE>{}, unsigned long long* trace = nullptr) {
   PA_CHECK((size_t)B * 64 * 64 * 64 * 2 < 0x7fffffffu, "stem: output over 2 GB");
   hipLaunchKernelGGL((stem_role_fp16<PBT, D, PRE, DBG, XM, BR, IL>), dim3(64 / PBT, B), dim3(stem::NT), 0, s, x, B, Cin, w, bias, out,
                      src, trace);
@@ -618,10 +687,28 @@ int launch_stem_pool_rgbd(const RgbdSrc& src, int B, const _Float16* w, const fl
   // (B = 3: 96 workgroups of 2 pooled rows instead of 12 of 16; same arithmetic per row)
   // (B <= 4: one pooled row per workgroup -- 192 workgroups at B = 3, 5.6 vs 6.7 us for two rows,
   // bit-identical, profiles/r04stem/)
-  if (B <= 4) return run_stem4<1, 2, true>(nullptr, B, 4, w, bias, out, s, src);
-  if (B <= 8) return run_stem4<2, 2, true>(nullptr, B, 4, w, bias, out, s, src);
-  if (B <= 24) return run_stem4<4, 2, true>(nullptr, B, 4, w, bias, out, s, src);
-  return run_stem4<16, 2, true>(nullptr, B, 4, w, bias, out, s, src);
+  if (B <= 4) return run_stem4<1, 2, SRC_RGBD>(nullptr, B, 4, w, bias, out, s, src);
+  if (B <= 8) return run_stem4<2, 2, SRC_RGBD>(nullptr, B, 4, w, bias, out, s, src);
+  if (B <= 24) return run_stem4<4, 2, SRC_RGBD>(nullptr, B, 4, w, bias, out, s, src);
+  return run_stem4<16, 2, SRC_RGBD>(nullptr, B, 4, w, bias, out, s, src);
+}
+
+// RGB-only frames straight into the stem (3-channel models): the band sizes by batch of
+// launch_stem_pool_rgbd; crop only and resize + crop are separate instantiations
+template <int PRE>
+static int stem_pool_rgb(const RgbSrc& src, int B, const _Float16* w, const float* bias, _Float16* out, hipStream_t s) {
+  if (B <= 4) return run_stem4<1, 2, PRE>(nullptr, B, 3, w, bias, out, s, src);
+  if (B <= 8) return run_stem4<2, 2, PRE>(nullptr, B, 3, w, bias, out, s, src);
+  if (B <= 24) return run_stem4<4, 2, PRE>(nullptr, B, 3, w, bias, out, s, src);
+  return run_stem4<16, 2, PRE>(nullptr, B, 3, w, bias, out, s, src);
+}
+
+int launch_stem_pool_rgb(const RgbSrc& src, int B, const _Float16* w, const float* bias, _Float16* out,
+                         hipStream_t s) {
+  PA_CHECK(src.rgb, "stem rgb: null frame pointer");
+  if (B <= 0) return PA_OK;
+  return src.resize ? stem_pool_rgb<SRC_RGB_RESIZE>(src, B, w, bias, out, s)
+                    : stem_pool_rgb<SRC_RGB>(src, B, w, bias, out, s);
 }
 
 int launch_stem_pool_fp16(const float* x, int B, int Cin, const _Float16* w, const float* bias, _Float16* out,
@@ -645,19 +732,19 @@ int launch_stem_pool_fp16(const float* x, int B, int Cin, const _Float16* w, con
       break;
     case 16: return run_stem3<16, 2, true>(x, B, Cin, w, bias, out, s);  // version 3 (shipped until round 2)
     case 24:
-      if (g_trace) return run_stem4<16, 2, false, 4>(x, B, Cin, w, bias, out, s, RgbdSrc{}, g_trace);  // timestamps
+      if (g_trace) return run_stem4<16, 2, SRC_F32, 4>(x, B, Cin, w, bias, out, s, RgbdSrc{}, g_trace);  // timestamps
       break;
 #if PA_TIMING_VARIANTS
-    case 26: return run_stem4<16, 2, false, 5>(x, B, Cin, w, bias, out, s);  // timing only: idle movers
+    case 26: return run_stem4<16, 2, SRC_F32, 5>(x, B, Cin, w, bias, out, s);  // timing only: idle movers
 #endif
     case 27: return run_stem4<8, 2>(x, B, Cin, w, bias, out, s);  // shorter bands at any batch (A/B)
     case 28: return run_stem4<4, 2>(x, B, Cin, w, bias, out, s);
     case 29: return run_stem4<32, 2>(x, B, Cin, w, bias, out, s);
-    case 30: return run_stem4<16, 2, false, 0, true>(x, B, Cin, w, bias, out, s);  // XCD-grouped bands
-    case 31: return run_stem4<16, 2, false, 0, false, true, false>(x, B, Cin, w, bias, out, s);  // BR alone
-    case 32: return run_stem4<16, 2, false, 0, false, true, true>(x, B, Cin, w, bias, out, s);  // BR + IL
-    case 33: return run_stem4<16, 2, false, 0, false, false, true>(x, B, Cin, w, bias, out, s);  // IL
-    case 34: return run_stem4<16, 2, false, 0, false, false, false>(x, B, Cin, w, bias, out, s);  // neither (round 4)
+    case 30: return run_stem4<16, 2, SRC_F32, 0, true>(x, B, Cin, w, bias, out, s);  // XCD-grouped bands
+    case 31: return run_stem4<16, 2, SRC_F32, 0, false, true, false>(x, B, Cin, w, bias, out, s);  // BR alone
+    case 32: return run_stem4<16, 2, SRC_F32, 0, false, true, true>(x, B, Cin, w, bias, out, s);  // BR + IL
+    case 33: return run_stem4<16, 2, SRC_F32, 0, false, false, true>(x, B, Cin, w, bias, out, s);  // IL
+    case 34: return run_stem4<16, 2, SRC_F32, 0, false, false, false>(x, B, Cin, w, bias, out, s);  // neither (round 4)
     // shipped: version 4, the role split (29.3 vs 31.8 us per B = 64 launch, bit-identical;
     // prefetch depth 3 / 4 measured 29.7 / 30.4 us)
     default: break;

@@ -207,7 +207,7 @@ class KeypointCNN(nn.Module):
 
     def reserve(self, max_batch: int, device=None):
         """pa_detector_reserve in this model's precision: the workspace (and for fp16x3 / fp32
-        the RGBD staging of forward_rgbd) for batches up to `max_batch`, so that a graph
+        the f32 staging of forward_rgbd / forward_rgb) for batches up to `max_batch`, so that a graph
         captured afterwards allocates nothing."""
         device = torch.device(device or torch.device("cuda", torch.cuda.current_device()))
         h = self._ensure_handle(device)
@@ -282,6 +282,71 @@ class KeypointCNN(nn.Module):
                                                   -1.0 if far is None else float(far), y.data_ptr(),
                                                   _lib.stream_of(dev)), "pa_detector_forward_rgbd")
         return y
+
+    def _rgb_args(self, rgb: torch.Tensor, what: str):
+        if rgb.device.type != "cuda":
+            raise RuntimeError(f"{what} expects a device tensor")
+        rgb = rgb.contiguous()
+        if rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[-1] != 3:
+            raise RuntimeError(f"expected uint8 (B,Hs,Ws,3), got {tuple(rgb.shape)} {rgb.dtype}")
+        h = self._ensure_handle(rgb.device)
+        _lib.check(_lib.lib().pa_detector_set_precision(h, _lib.precision_code(self.precision)), "set_precision")
+        return rgb, h
+
+    def forward_rgb(self, rgb: torch.Tensor, bgr: bool = True, resize_short: int = 0,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+        """RGB-only frames -> keypoints for a 3-channel model (scripts/streaming.py:104,112-128;
+        validate_real.py:62-74): uint8 (B,Hs,Ws,3) on the GPU, `/255`, centre crop to 256x256, or
+        with resize_short = S >= 256 kornia's resize to a short side of S first
+        (pa_detector_forward_rgb).  fp16: inside the stem's row loads (no f32 input tensor);
+        fp16x3 / fp32: the preprocess kernel into the handle's staging, then the forward.  All
+        give the bits of forward(preprocess_rgb(rgb, ...)).  `out` as in forward()."""
+        rgb, h = self._rgb_args(rgb, "forward_rgb")
+        B, Hs, Ws, _ = rgb.shape
+        dev = rgb.device
+        shape = (B, 2 * self.n_keypoints)
+        if out is not None:
+            if (out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != shape
+                    or not out.is_contiguous()):
+                raise RuntimeError(f"out must be a contiguous float32 {shape} tensor on {dev}")
+            y = out
+        else:
+            y = torch.empty(shape, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().pa_detector_forward_rgb(h, rgb.data_ptr(), B, Hs, Ws, int(bgr), int(resize_short),
+                                                          y.data_ptr(), _lib.stream_of(dev)), "pa_detector_forward_rgb")
+        return y
+
+    def forward_real(self, rgb) -> torch.Tensor:
+        """validate_real.py:62-74 on RGB images of any size: uint8 (B,Hs,Ws,3) or (Hs,Ws,3), RGB
+        byte order (a tensor or an array; host data is copied to the current GPU and the result
+        comes back on the input's device).  A source already (H, W) is taken as it is; any other is
+        resized to a short side of int(1.8 * H) and centre-cropped (:69-71)."""
+        rgb = torch.as_tensor(rgb)
+        if rgb.dim() == 3:
+            rgb = rgb[None]
+        out_dev = rgb.device
+        if rgb.device.type != "cuda":
+            if not torch.cuda.is_available():
+                raise RuntimeError("perseus_amd.KeypointCNN needs a ROCm GPU (no CPU fallback)")
+            rgb = rgb.to(torch.device("cuda", torch.cuda.current_device()))
+        same = tuple(rgb.shape[1:3]) == (self.H, self.W)
+        y = self.forward_rgb(rgb, bgr=False, resize_short=0 if same else int(1.8 * self.H))
+        return y if out_dev == rgb.device else y.to(out_dev)
+
+    def profile_rgb(self, rgb: torch.Tensor, bgr: bool = True, resize_short: int = 0, max_kernels: int = 64):
+        """profile() of forward_rgb: per-kernel device times (ms) and the keypoints."""
+        rgb, h = self._rgb_args(rgb, "profile_rgb")
+        B, Hs, Ws, _ = rgb.shape
+        dev = rgb.device
+        y = torch.full((B, 2 * self.n_keypoints), float("nan"), dtype=torch.float32, device=dev)
+        ms = (_lib.C.c_float * max_kernels)()
+        names = (_lib.C.c_char_p * max_kernels)()
+        with torch.cuda.device(dev):
+            n = _lib.check(_lib.lib().pa_detector_profile_rgb(h, rgb.data_ptr(), B, Hs, Ws, int(bgr),
+                                                              int(resize_short), y.data_ptr(), _lib.stream_of(dev),
+                                                              ms, names, max_kernels), "pa_detector_profile_rgb")
+        return [(names[i].decode(), ms[i]) for i in range(n)], y
 
     def profile(self, x: torch.Tensor, max_kernels: int = 64):
         """Per-kernel device times (ms) of one forward, via HIP events in the library."""
@@ -387,4 +452,34 @@ def preprocess_rgbd(rgb: torch.Tensor, depth: torch.Tensor, H: int = 256, W: int
     _lib.check(_lib.lib().pa_preprocess_rgbd(rgb.data_ptr(), depth.data_ptr(), B, Hs, Ws, int(bgr),
                                              -1.0 if near is None else near, -1.0 if far is None else far,
                                              H, W, x.data_ptr(), _lib.stream_of(rgb.device)), "preprocess")
+    return x
+
+
+def real_image_size(Hs: int, Ws: int, S: int) -> "tuple[int, int]":
+    """(Hr, Wr) of kornia.geometry.transform.resize(image, S, side="short") for an (Hs, Ws)
+    image (validate_real.py:69; written from kornia's published source): the
+    short side becomes S, the other S scaled by the aspect ratio and truncated.  The library's
+    host side computes the same (csrc/conv.hip real_image_size)."""
+    ar = float(Ws) / float(Hs)
+    if ar < 1.0:
+        return int(S / ar), int(S)
+    return int(S), int(S * ar)
+
+
+def preprocess_rgb(rgb: torch.Tensor, H: int = 256, W: int = 256, bgr: bool = True,
+                   resize_short: int = 0) -> torch.Tensor:
+    """The model input of forward_rgb alone (pa_preprocess_rgb): uint8 (B,Hs,Ws,3) on the GPU ->
+    (B,3,H,W) f32: `/255` and the centre crop, or with resize_short = S >= 256 `/255`, the
+    bilinear resize to a short side of S (torch.nn.functional.interpolate's arithmetic,
+    align_corners=False) and the centre crop of the resized image."""
+    if rgb.device.type != "cuda":
+        raise RuntimeError("preprocess_rgb expects a device tensor")
+    rgb = rgb.contiguous()
+    if rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[-1] != 3:
+        raise RuntimeError(f"expected uint8 (B,Hs,Ws,3), got {tuple(rgb.shape)} {rgb.dtype}")
+    B, Hs, Ws, _ = rgb.shape
+    x = torch.empty((B, 3, H, W), dtype=torch.float32, device=rgb.device)
+    with torch.cuda.device(rgb.device):
+        _lib.check(_lib.lib().pa_preprocess_rgb(rgb.data_ptr(), B, Hs, Ws, int(bgr), int(resize_short), H, W,
+                                                x.data_ptr(), _lib.stream_of(rgb.device)), "preprocess_rgb")
     return x

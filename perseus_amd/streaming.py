@@ -29,6 +29,10 @@ Gauss-Newton step per tick.  Per tick:
        else one D2H), one H2D of [rgb | depth] at the start (or zero-copy reads of it)
   host: wait for the replay, return (n_cams, K, 2) pixel coordinates (and the poses).
 
+A 3-channel (RGB) model runs the same tick on the colour frames alone, as streaming.py does
+with `frame[:C]`: the staging block holds [rgb] only, a depth argument is ignored, and the
+detector call is pa_detector_forward_rgb_px (crop only).
+
 The graph removes the per-launch CPU cost of the ~26 launches (the forward at B=3
 is launch-bound, not compute-bound).  Workspace and every pose-stage buffer are
 allocated before capture so no allocation happens inside the graph.
@@ -64,6 +68,13 @@ class StreamingPipeline:
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingPipeline needs a ROCm GPU (no CPU fallback)")
         cam_K = K  # (the name K is the keypoint count below)
+        # a 3-channel model takes the RGB half of each frame (scripts/streaming.py:104,126 with an
+        # RGB model feeds frame[:C]: the depth is dropped): RGB-only staging, pa_detector_forward_rgb_px
+        if model.num_channels not in (3, 4):
+            raise ValueError("StreamingPipeline feeds RGBD (num_channels=4) or RGB (num_channels=3)")
+        self.rgb_only = model.num_channels == 3
+        if self.rgb_only and (near is not None or far is not None):
+            raise ValueError("near / far clip the depth channel: an RGB model (num_channels=3) has none")
         self.dev = torch.device(device or torch.device("cuda", torch.cuda.current_device()))
         self.model = model
         self.n = n_cams
@@ -83,10 +94,11 @@ class StreamingPipeline:
         # ~5-12 us operation on the stream, and a copy enqueued between kernels stalls them):
         #   in  = [rgb (n, sh, sw, 3) u8 | depth (n, sh, sw) f32]
         #   out = [px (n, K, 2) f32 | info (n,) i32 | pad to 8 B | newest pose (n, 12) f64]
+        # (RGB model: in = [rgb] alone)
         nr = n * sh * sw * 3
-        if nr % 4:
+        if nr % 4 and not self.rgb_only:
             raise ValueError(f"staging: {n} x {sh} x {sw} RGB bytes not 4-aligned for the depth block")
-        nin = nr + n * sh * sw * 4
+        nin = nr if self.rgb_only else nr + n * sh * sw * 4
         self._po = ((n * K * 2 + n) * 4 + 7) // 8 * 8
         self._px_bytes = n * K * 8
         nout = self._po + n * 12 * 8
@@ -96,7 +108,8 @@ class StreamingPipeline:
         self.out_d = torch.zeros(nout, dtype=torch.uint8, device=self.dev)
 
         def views(i, o):
-            return (i[:nr].view(n, sh, sw, 3), i[nr:].view(torch.float32).view(n, sh, sw),
+            return (i[:nr].view(n, sh, sw, 3),
+                    None if self.rgb_only else i[nr:].view(torch.float32).view(n, sh, sw),
                     o[:n * K * 8].view(torch.float32).view(n, K, 2),
                     o[n * K * 8:n * K * 8 + n * 4].view(torch.int32),
                     o[self._po:].view(torch.float64).view(n, 12))
@@ -108,7 +121,7 @@ class StreamingPipeline:
         # coalesced reads beat the copy: fp16x3 pose tick 0.330 -> 0.322 ms device), off for fp16
         # (the stem's row loads over PCIe lose: 0.252 -> 0.267 ms; profiles/r04v/)
         self.zero_copy = (model.precision != "fp16") if zero_copy is None else bool(zero_copy)
-        self._src = (self.rgb_d.data_ptr(), self.depth_d.data_ptr())
+        self._src = (self.rgb_d.data_ptr(), None if self.rgb_only else self.depth_d.data_ptr())
         if self.zero_copy:
             dp = C.c_void_p()
             _lib.check(_lib.lib().pa_host_device_pointer(C.c_void_p(self.in_h.data_ptr()), C.byref(dp)),
@@ -142,8 +155,6 @@ class StreamingPipeline:
         # fp16 and fp16x3, fp32 has no such mode)
         self.split_k = bool(split_k) and n <= 64 and model.precision != "fp32"
         _lib.check(L.pa_detector_set_split_k(self._h, n if self.split_k else 0), "set_split_k")
-        if model.num_channels != 4:
-            raise ValueError("StreamingPipeline feeds RGBD (num_channels=4)")
         self.pose_L = int(pose_window)
         self._split_pose_req = bool(split_pose)
         self._pre_ahead_req = bool(pre_ahead)
@@ -190,10 +201,15 @@ class StreamingPipeline:
                 self.in_d.copy_(self.in_h, non_blocking=True)
             # fp16: the preprocess runs inside the stem's row loads; fp16x3 / fp32: the
             # preprocess kernel into the handle's staging, then the forward; the denormalize in the head
-            _lib.check(L.pa_detector_forward_rgbd_px(self._h, self._src[0], self._src[1], self.n,
-                                                     self.sh, self.sw, int(self.bgr), self.near, self.far,
-                                                     self.y.data_ptr(), self._px_out, fw.cuda_stream),
-                       "forward_rgbd_px")
+            if self.rgb_only:  # the same with the RGB source (crop only: the cameras deliver >= 256 x 256)
+                _lib.check(L.pa_detector_forward_rgb_px(self._h, self._src[0], self.n, self.sh, self.sw,
+                                                        int(self.bgr), 0, self.y.data_ptr(), self._px_out,
+                                                        fw.cuda_stream), "forward_rgb_px")
+            else:
+                _lib.check(L.pa_detector_forward_rgbd_px(self._h, self._src[0], self._src[1], self.n,
+                                                         self.sh, self.sw, int(self.bgr), self.near, self.far,
+                                                         self.y.data_ptr(), self._px_out, fw.cuda_stream),
+                           "forward_rgbd_px")
         if split:
             self._enqueue_pose_pre()
             cur.wait_stream(self.side)
@@ -313,9 +329,21 @@ class StreamingPipeline:
         self.stream.synchronize()
         return {k: v.cpu().numpy().copy() for k, v in self.win.items()}
 
-    def stage(self, rgb: np.ndarray, depth: np.ndarray) -> None:
+    def stage(self, rgb: np.ndarray, depth: np.ndarray | None = None) -> None:
         """Copy one tick of camera frames (n, Hs, Ws, 3) uint8 + (n, Hs, Ws) f32 metres
-        into the pinned staging buffers (centre crop only when host_crop)."""
+        into the pinned staging buffers (centre crop only when host_crop).  An RGB model
+        stages the colour frames alone; a depth argument is ignored."""
+        if self.rgb_only:
+            if rgb.shape != (self.n, self.Hs, self.Ws, 3):
+                raise ValueError(f"expected ({self.n},{self.Hs},{self.Ws},3) rgb")
+            if self.host_crop:
+                r0, c0 = self.r0, self.c0
+                self.rgb_h.numpy()[:] = rgb[:, r0:r0 + self.H, c0:c0 + self.W]
+            else:
+                self.rgb_h.numpy()[:] = rgb
+            return
+        if depth is None:
+            raise ValueError("an RGBD model (num_channels=4) needs the depth frames")
         if rgb.shape != (self.n, self.Hs, self.Ws, 3) or depth.shape != (self.n, self.Hs, self.Ws):
             raise ValueError(f"expected ({self.n},{self.Hs},{self.Ws},3) rgb and ({self.n},{self.Hs},{self.Ws}) depth")
         if self.host_crop:
@@ -353,11 +381,11 @@ class StreamingPipeline:
             self.stream.synchronize()
         return self.px_h.numpy().copy()
 
-    def __call__(self, rgb: np.ndarray, depth: np.ndarray) -> np.ndarray:
+    def __call__(self, rgb: np.ndarray, depth: np.ndarray | None = None) -> np.ndarray:
         self.stage(rgb, depth)
         return self.run()
 
-    def tick(self, rgb: np.ndarray, depth: np.ndarray):
+    def tick(self, rgb: np.ndarray, depth: np.ndarray | None = None):
         """One camera tick through the pose stage: (pixels (n, K, 2), newest pose of each
         camera's window (n, 12: R row-major, t), GN info (n,) int32, 0 = solved).
 
