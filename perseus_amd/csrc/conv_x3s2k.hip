@@ -10,8 +10,8 @@
 // 33 columns x [hi 128 | lo 128] of both blocks, 272-byte positions per block) is double-
 // buffered.  Per (tap, 32-channel half) group a wave reads the x_hi and x_lo fragments of its
 // block (2 ds_read_b128) for 3 MFMAs, read two groups ahead (one 16-pixel fragment per wave:
-// 48 MFMA cycles per group would not cover the LDS latency at one group ahead, as conv_s2k.hip's
-// layer4 form showed); the three products go to three accumulators (x_hi w_hi, x_hi w_lo,
+// 48 MFMA cycles per group do not cover the LDS latency at one group ahead);
+// the three products go to three accumulators (x_hi w_hi, x_hi w_lo,
 // x_lo w_hi: no back-to-back dependent MFMAs).  At the end of a tile the block-1 waves hand their
 // conv partial and the block-0 waves their downsample partial over through LDS, and each
 // finalizes one: (block 0 + block 1), each block's (hh + lh) + hl.

@@ -32,7 +32,6 @@ struct ConvL {
   size_t w_off;   // element offset into the packed weight arrays (w16 / w32)
   size_t b_off;   // element offset into the bias / scale arrays
   size_t w3_off;  // element offset into the fp16x3 weight planes (w3)
-  long wk_off = -1;  // layer2 3x3 s1 convs: element offset into pa_detector::wk2 (conv_s1k.hip order)
 };
 
 struct Block {
@@ -41,8 +40,6 @@ struct Block {
 
 // conv_gx.h xperm on the host (weight packing)
 static inline int xperm_host(int rho) { return (rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3); }
-// layer2's 3x3 s1 convs with the weights in VGPRs (conv_s1k.hip)
-int launch_conv3x3_s1k(const ConvArgs& a, const _Float16* wk, int variant, hipStream_t s, const char** kname);
 
 }  // namespace pa
 
@@ -54,11 +51,8 @@ struct pa_detector {
   float* w32 = nullptr;
   float* bias = nullptr;
   _Float16* wv2 = nullptr;  // layer2 entry (conv 3x3 s2 + ds, 64 -> 128) in VGPR-fragment order (conv_s2v.hip)
-  _Float16* wv3 = nullptr;  // layer3 / layer4 entries (128 -> 256, 256 -> 512) in conv_s2k.hip's order
-  _Float16* wv4 = nullptr;
   _Float16* wv2x3 = nullptr;  // fp16x3 layer2 entry's hi / lo planes in conv_x3s2v.hip's register order
   _Float16* wv3x3 = nullptr;  // fp16x3 layer3 entry's in conv_x3s2k.hip's order
-  _Float16* wk2 = nullptr;    // layer2's three 3x3 s1 convs in conv_s1k.hip's register order
   _Float16* w3 = nullptr;   // fp16x3: per conv [cout][taps][hi (cin) | lo (cin)] of w * 2^e (stem: hi plane, lo plane)
   float* scl = nullptr;     // fp16x3: 2^-e per output channel (indexed like bias)
   float* bstem3 = nullptr;  // fp16x3 stem: bias * 2^e (the stem's accumulator starts from it)
@@ -204,76 +198,27 @@ static int build(pa_detector* d, const float* blob, size_t nfloats) {
   PA_HIP(hipMemcpy(d->bias, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice));
   PA_HIP(hipMemcpy(d->fcw, fw, (size_t)nout * 512 * sizeof(float), hipMemcpyHostToDevice));
   PA_HIP(hipMemcpy(d->fcb, fb, (size_t)nout * sizeof(float), hipMemcpyHostToDevice));
-  // the layer2 entry's conv + downsample weights in conv_s2v.hip's register order: for wave wn
-  // (channel quarter), fragment k (< 18: tap k / 2, 32-channel half k & 1; 18, 19: the downsample's
-  // halves), tile tn, lane (q, r16): 8 fp16 of channel xperm(32 wn + 16 tn + r16), input channels
-  // 32 h + 8 q .. + 7 -- each wave-instruction loads 1 KB contiguous straight into the VGPRs the
-  // MFMA reads (no LDS staging)
-  // The layer3 / layer4 entries' in conv_s2k.hip's order (the same per wave, for its 64-channel
-  // input block wb and its workgroup's channel half h): [h][wb][wn][fragment 20][tn 2][lane 64][8]
-  // of channel 32 WN h + xperm(32 wn + 16 tn + r16), input channels 64 wb + 32 (k & 1) + 8 q + e.
-  auto pack_vgpr = [&](const Block& bk, int wnq, _Float16** dst) -> int {
-    const ConvL& c = d->convs[bk.conv1];
-    const ConvL& cd = d->convs[bk.ds];
-    const int nb = c.cin / 64, nh = c.cout / (32 * wnq);
-    std::vector<_Float16> hv((size_t)nh * nb * wnq * 20 * 2 * 64 * 8);
-    for (int hh = 0; hh < nh; ++hh)
-      for (int wb = 0; wb < nb; ++wb)
-        for (int wn = 0; wn < wnq; ++wn)
-          for (int k = 0; k < 20; ++k)
-            for (int tn = 0; tn < 2; ++tn)
-              for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                  const int q = lane >> 4, r16 = lane & 15;
-                  const int rho = 32 * wn + 16 * tn + r16;
-                  const int co = 32 * wnq * hh + ((rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) |
-                                                  (rho & 3));  // xperm
-                  const int ci = 64 * wb + 32 * (k & 1) + 8 * q + e;
-                  const _Float16 v = k < 18 ? h16[c.w_off + (size_t)co * 9 * c.cin + (size_t)(k >> 1) * c.cin + ci]
-                                            : h16[cd.w_off + (size_t)co * c.cin + ci];
-                  hv[((((((size_t)hh * nb + wb) * wnq + wn) * 20 + k) * 2 + tn) * 64 + lane) * 8 + e] = v;
-                }
-    PA_HIP(hipMalloc(dst, hv.size() * sizeof(_Float16)));
-    PA_HIP(hipMemcpy(*dst, hv.data(), hv.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    return PA_OK;
-  };
+  // the layer2 entry's conv + downsample weights in conv_s2v.hip's register order: [wave 4][fragment
+  // 20][tile 2][lane 64][8] of channel xperm(32 wn + 16 tn + r16), input channels 32 (k & 1) + 8 q + e
+  // (fragment k < 18: tap k / 2; 18, 19: the downsample)
   for (const Block& bk : d->blocks) {
-    if (bk.ds < 0) continue;
     const ConvL& c = d->convs[bk.conv1];
-    int rc = PA_OK;
-    if (c.cin == 64 && c.cout == 128 && !d->wv2) rc = pack_vgpr(bk, 4, &d->wv2);
-    if (c.cin == 128 && c.cout == 256 && !d->wv3) rc = pack_vgpr(bk, 4, &d->wv3);
-    if (c.cin == 256 && c.cout == 512 && !d->wv4) rc = pack_vgpr(bk, 2, &d->wv4);
-    if (rc != PA_OK) return rc;
-  }
-  // layer2's 3x3 stride-1 convs (128 -> 128) in conv_s1k.hip's order: per conv [h 2][wb 2][wn 2]
-  // [fragment 18][tn 2][lane 64][8] of channel 64 h + xperm(32 wn + 16 tn + r16), input channels
-  // 64 wb + 32 (k & 1) + 8 q + e, tap k / 2
-  {
-    std::vector<_Float16> hv;
-    for (pa::ConvL& c : d->convs) {
-      if (c.cin != 128 || c.cout != 128 || c.ks != 3 || c.stride != 1) continue;
-      c.wk_off = (long)hv.size();
-      hv.resize(hv.size() + (size_t)2 * 2 * 2 * 18 * 2 * 64 * 8);
-      _Float16* dst = hv.data() + c.wk_off;
-      for (int hh = 0; hh < 2; ++hh)
-        for (int wb = 0; wb < 2; ++wb)
-          for (int wn = 0; wn < 2; ++wn)
-            for (int k = 0; k < 18; ++k)
-              for (int tn = 0; tn < 2; ++tn)
-                for (int lane = 0; lane < 64; ++lane)
-                  for (int e = 0; e < 8; ++e) {
-                    const int q = lane >> 4, r16 = lane & 15;
-                    const int co = 64 * hh + pa::xperm_host(32 * wn + 16 * tn + r16);
-                    const int ci = 64 * wb + 32 * (k & 1) + 8 * q + e;
-                    dst[((((((size_t)hh * 2 + wb) * 2 + wn) * 18 + k) * 2 + tn) * 64 + lane) * 8 + e] =
-                        h16[c.w_off + (size_t)co * 9 * 128 + (size_t)(k >> 1) * 128 + ci];
-                  }
-    }
-    if (!hv.empty()) {
-      PA_HIP(hipMalloc(&d->wk2, hv.size() * sizeof(_Float16)));
-      PA_HIP(hipMemcpy(d->wk2, hv.data(), hv.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
+    if (bk.ds < 0 || c.cin != 64 || c.cout != 128 || d->wv2) continue;
+    const ConvL& cd = d->convs[bk.ds];
+    std::vector<_Float16> hv((size_t)4 * 20 * 2 * 64 * 8);
+    for (int wn = 0; wn < 4; ++wn)
+      for (int k = 0; k < 20; ++k)
+        for (int tn = 0; tn < 2; ++tn)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int e = 0; e < 8; ++e) {
+              const int q = lane >> 4, r16 = lane & 15, co = xperm_host(32 * wn + 16 * tn + r16);
+              const int ci = 32 * (k & 1) + 8 * q + e;
+              const _Float16 v = k < 18 ? h16[c.w_off + ((size_t)co * 9 + (k >> 1)) * 64 + ci]
+                                        : h16[cd.w_off + (size_t)co * 64 + ci];
+              hv[((((size_t)wn * 20 + k) * 2 + tn) * 64 + lane) * 8 + e] = v;
+            }
+    PA_HIP(hipMalloc(&d->wv2, hv.size() * sizeof(_Float16)));
+    PA_HIP(hipMemcpy(d->wv2, hv.data(), hv.size() * sizeof(_Float16), hipMemcpyHostToDevice));
   }
   // the fp16x3 layer2 entry's hi / lo planes in conv_x3s2v.hip's register order: [wave 8][fragment
   // 20][plane 2][lane 64][8] of channel 16 wave + r16, input channels 32 (k & 1) + 8 q + e (fragment
@@ -454,11 +399,12 @@ static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_
   // g_variant[7] == 3: avgpool + fc fused into layer4's last conv (conv_gx.h gx_head).
   // Bit-identical to the separate head_fp16 and measured neutral (27.3 us for the fused
   // launch vs 19.5 + 6.7 us; 176.7k vs 177.3k frames/s interleaved), so not shipped.  It runs
-  // with layer4 on its one-K-group form (4:65; the shipped K split has no fused head).
+  // with layer4 on its shipped one-K-group form (the default id, or 4:65 by name; the K split,
+  // 4:67, has no fused head).
   bool fuse_head = false;
   if constexpr (std::is_same<T, _Float16>::value)
-    fuse_head = g_variant[7] == 3 && g_variant[4] == 65 && d->n_kp == 8 && d->H == 256 && d->W == 256 &&
-                d->blocks.back().ds < 0;
+    fuse_head = g_variant[7] == 3 && (g_variant[4] == 0 || g_variant[4] == 65) && d->n_kp == 8 && d->H == 256 &&
+                d->W == 256 && d->blocks.back().ds < 0;
   if (prof) prof->mark("start");
   const ConvL& st = d->convs[0];
   if constexpr (std::is_same<T, _Float16>::value) {
@@ -477,13 +423,10 @@ static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_
   int launch = 1;  // stem = 0
   auto trace = [&]() { return g_trace ? g_trace + (size_t)TRACE_LAUNCH * launch++ : nullptr; };
   // stride-1 convs: split-K form for small batches (pa_detector_set_split_k, conv_splitk.hip)
-  auto conv_s1 = [&](ConvArgs& a, const char** kn, const ConvL& cl) -> int {
+  auto conv_s1 = [&](ConvArgs& a, const char** kn) -> int {
     if (!(a.epi & EPI_HEAD)) a.cnt = d->tctr;  // (only conv_c64v.hip reads it)
     if constexpr (std::is_same<T, _Float16>::value) {
       const int layer = a.Hout == 64 ? 1 : a.Hout == 32 ? 2 : a.Hout == 16 ? 3 : a.Hout == 8 ? 4 : 0;
-      // 2:80 - 2:82 (A/B): layer2 on conv_s1k.hip (weights in VGPRs, K split over the waves)
-      if (layer == 2 && g_variant[2] >= 80 && g_variant[2] <= 82 && d->wk2 && cl.wk_off >= 0)
-        return launch_conv3x3_s1k(a, d->wk2 + cl.wk_off, g_variant[2] - 80, s, kn);
       // g_variant[layer] == 71 (A/B): layer2 split as well, layer1 on the persistent kernel
       if (layer && small && (g_variant[layer] == 0 || g_variant[layer] == 71 || (g_variant[layer] >= 35 &&
                                                                                    g_variant[layer] <= 39)) &&
@@ -522,10 +465,7 @@ static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_
       sa.wds = wts + cd.w_off;
       sa.bias2 = d->bias + cd.b_off;
       if constexpr (std::is_same<T, _Float16>::value)
-        sa.wfrag = (c1.cin == 64 && c1.cout == 128)    ? d->wv2   // conv_s2v.hip
-                   : (c1.cin == 128 && c1.cout == 256) ? d->wv3   // conv_s2k.hip
-                   : (c1.cin == 256 && c1.cout == 512) ? d->wv4
-                                                       : nullptr;
+        sa.wfrag = (c1.cin == 64 && c1.cout == 128) ? d->wv2 : nullptr;  // conv_s2v.hip
       sa.out = Tb;
       sa.out2 = D;
       sa.B = B;
@@ -565,7 +505,7 @@ static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_
       a.epi = EPI_RELU;
       a.trace = trace();
       if (c1.stride == 1)
-        PA_RUN(conv_s1(a, &kn, c1), kn);
+        PA_RUN(conv_s1(a, &kn), kn);
       else
         PA_RUN(launch_conv<T>(a, 3, s, &kn), kn);
       if (b.ds >= 0) {
@@ -608,7 +548,7 @@ static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_
       b2.fcb = d->fcb;
       b2.y = y;
     }
-    PA_RUN(conv_s1(b2, &kn, c2), kn);
+    PA_RUN(conv_s1(b2, &kn), kn);
     if (b.ds >= 0) std::swap(X, D);
     hw = ho;
   }
@@ -993,11 +933,8 @@ void pa_detector_destroy(pa_detector* d) {
   hipFree(d->fcb);
   hipFree(d->w3);
   if (d->wv2) hipFree(d->wv2);
-  if (d->wv3) hipFree(d->wv3);
-  if (d->wv4) hipFree(d->wv4);
   if (d->wv2x3) hipFree(d->wv2x3);
   if (d->wv3x3) hipFree(d->wv3x3);
-  if (d->wk2) hipFree(d->wk2);
   hipFree(d->scl);
   hipFree(d->bstem3);
   if (d->ws) hipFree(d->ws);
@@ -1144,6 +1081,11 @@ int pa_detector_debug_set_variant(pa_detector* d, int layer, int variant) {
   PA_CHECK(PA_TIMING_VARIANTS || !timing_only_variant(layer, variant),
            "variant %d:%d is timing-only (wrong results): not in the release library (build with "
            "PERSEUS_AMD_TIMING_VARIANTS=1)", layer, variant);
+  // 2:80-82 and 6:55 / 6:56 (weights in VGPRs, K split over the waves): measured slower,
+  // never shipped, deleted
+  PA_CHECK(!(layer == 2 && variant >= 80 && variant <= 82) && !(layer == 6 && (variant == 55 || variant == 56)),
+           "variant %d:%d was removed with its kernel; the last commit that has it is \"Add the RGB-only frame "
+           "path: uint8 RGB, optional resize, fused 3-ch stem\"", layer, variant);
   PA_CHECK(d, "null detector");
   d->variant[layer] = variant;
   return PA_OK;

@@ -91,7 +91,8 @@ def test_timing_only_variants_rejected_by_release_library():
     """The wrong-result timing variants (csrc/common.h PA_TIMING_VARIANTS) are not in the release
     library: pa_detector_debug_set_variant refuses their ids before it looks at the handle, so no
     public call can select them.  Shipped-alternative ids pass that check and
-    then fail only on the NULL handle.  No GPU call is made."""
+    then fail only on the NULL handle.  The ids of kernels deleted from the tree are refused the same
+    way, instead of falling through to some other kernel.  No GPU call is made."""
     from perseus_amd import _lib
 
     L = _lib.lib()
@@ -102,3 +103,6 @@ def test_timing_only_variants_rejected_by_release_library():
     for layer, v in ((0, 34), (1, 80), (1, 60), (3, 53), (4, 58), (6, 41)):
         assert L.pa_detector_debug_set_variant(None, layer, v) < 0
         assert b"null detector" in L.pa_last_error(), (layer, v)
+    for layer, v in ((2, 80), (2, 81), (2, 82), (6, 55), (6, 56)):
+        assert L.pa_detector_debug_set_variant(None, layer, v) < 0
+        assert b"removed" in L.pa_last_error(), (layer, v)
