@@ -261,6 +261,59 @@ int pa_trajectory_gn_step(int T, int L, int n_kp, const double* r_proj, const do
                           const double* j_cv0, const double* j_cv1, double lambda, double* D, double* E, double* g,
                           double* delta, int32_t* info, void* ws, size_t ws_bytes, void* stream);
 
+/* Levenberg-Marquardt over the same graph (what GTSAM's LevenbergMarquardtOptimizer::optimize
+ * does on the host for the reference's users), per trajectory and independently, all on the
+ * device: 1 + 2 max_iters launches on `stream`, no host synchronisation (capturable).
+ * args: the pa_traj_args of pa_trajectory_linearize; all three isig_* are required (the cost is
+ * defined on whitened residuals), as is every factor output and Jacobian pointer; n_kp >= 1;
+ * nvalid is honoured.  args->pose / vel / angvel are updated IN PLACE to the final accepted
+ * state, and on return the factor outputs hold the linearization at that state.
+ *   1. C = sum of err (0.5 |r_w|^2) over the dynamics and constant-velocity factors and the
+ *      projection factors with status 0 at the state x; lambda = lambda0; cost0 = cost_hist[0] = C.
+ *   2. iteration k = 1..max_iters: (J^T J + lambda I) delta = -J^T r (pa_trajectory_gn_step's
+ *      system).  A failed pivot rejects the step.  Else x' = retract(x, delta) (pa_window_retract's
+ *      arithmetic), C' = the cost at x'; x' is rejected if a projection factor with status 0 at x
+ *      has status 1 (cheirality) at x'; otherwise it is accepted iff C' < C.
+ *   3. accept: x = x', lambda = max(lambda / lambda_down, lambda_min), status CONVERGED and stop
+ *      if C - C' <= rel_tol * C + abs_tol; then C = C'.
+ *   4. reject: lambda *= lambda_up, status STALLED and stop if that exceeds lambda_max; x stays.
+ *   5. cost_hist[k] = C after the decision; entries after the stop are NaN.
+ * A trajectory still running after iteration max_iters stops with MAX_ITERS.
+ * Outputs (device, per trajectory): cost0, cost (final), iters (trial steps taken), status
+ * (PA_LM_*), lambda (final; on STALLED the value that exceeded lambda_max), cost_hist
+ * (T, max_iters + 1) or NULL.  2 <= L <= 24, 1 <= n_kp <= 16, any T >= 1 (one workgroup per
+ * trajectory); a finished trajectory's workgroups return at once in the later launches.
+ * Everything else returns PA_EINVAL before any launch; T = 0 is a no-op.
+ * ws: pa_trajectory_lm_workspace bytes (0 for shapes outside the limits), 16-byte aligned. */
+typedef struct pa_lm_params {
+  int max_iters;        /* >= 1; every trial step, accepted or not, counts as one */
+  double lambda0;       /* > 0 initial damping, per trajectory */
+  double lambda_up;     /* > 1, on reject / failed pivot */
+  double lambda_down;   /* > 1, on accept: lambda /= lambda_down */
+  double lambda_min, lambda_max;
+  double rel_tol, abs_tol; /* stop after an ACCEPTED step with C - C' <= rel_tol*C + abs_tol */
+} pa_lm_params;
+
+#define PA_LM_CONVERGED 1   /* stopped by rel_tol / abs_tol                  */
+#define PA_LM_MAX_ITERS 2   /* ran out of iterations                          */
+#define PA_LM_STALLED   3   /* lambda would exceed lambda_max                 */
+
+size_t pa_trajectory_lm_workspace(int T, int L, int n_kp, int max_iters);
+int pa_trajectory_lm_solve(const pa_traj_args* args, const pa_lm_params* p,
+                           double* cost0_dev, double* cost_dev, int32_t* iters_dev,
+                           int32_t* status_dev, double* lambda_dev,
+                           double* cost_hist_dev /* (T, max_iters+1) or NULL */,
+                           void* ws_dev, size_t ws_bytes, void* stream);
+/* The same solve on a streaming window.  newest_pending != 0: the window is the one
+ * pa_window_pose_tick_pre leaves between ticks (advanced, frame L-1 predicted, its keypoint slot
+ * still stale): frame L-1's projection factors get status 3 and stay out of the cost, the guard
+ * and the step, so frame L-1 is held by its dynamics factor alone.  On return the factor outputs
+ * are what the pre half's linearize leaves at the solved window; pa_window_pose_tick_reduce then
+ * rebuilds the reduced system for the post half.  newest_pending = 0: pa_trajectory_lm_solve. */
+int pa_window_lm_solve(const pa_traj_args* args, const pa_lm_params* p, int newest_pending,
+                       double* cost0_dev, double* cost_dev, int32_t* iters_dev, int32_t* status_dev,
+                       double* lambda_dev, double* cost_hist_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
 /* Fixed-lag window of the config-4 streaming pose stage (the smoother loop the reference
  * leaves to downstream GTSAM code; scripts/streaming.py:121-155 runs the detector only).
  * Per trajectory t the window holds frames l = 0..L-1 of y (T*L, 2K) f32, pose (T*L, 12),
@@ -313,6 +366,11 @@ size_t pa_window_pose_tick_workspace(int T, int L);
 int pa_window_pose_tick_pre(const pa_traj_args* args, double lambda, void* ws_dev, size_t ws_bytes, void* stream);
 int pa_window_pose_tick_post(const pa_traj_args* args, const float* y_new_dev, const void* ws_dev, size_t ws_bytes,
                              double* delta_dev, int32_t* info_dev, double* newest_pose_dev, void* stream);
+/* The second launch of pa_window_pose_tick_pre alone: the GN system assembled from the factor
+ * outputs AS THEY STAND and reduced to frame L-1 into ws; the window does not advance and nothing
+ * is linearized.  After pa_window_pose_tick_pre it rewrites the same ws bit for bit; after
+ * pa_window_lm_solve (newest_pending) it prepares the post half for the solved window. */
+int pa_window_pose_tick_reduce(const pa_traj_args* args, double lambda, void* ws_dev, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -34,8 +34,26 @@ class TrajArgs(C.Structure):
                 ("j_cv0", C.c_void_p), ("j_cv1", C.c_void_p), ("err_cv", C.c_void_p), ("nvalid", C.c_void_p)]
 
 
+class LMParams(C.Structure):
+    """Mirror of `pa_lm_params` (include/perseus_amd.h)."""
+
+    _fields_ = [("max_iters", C.c_int), ("lambda0", C.c_double), ("lambda_up", C.c_double),
+                ("lambda_down", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double),
+                ("rel_tol", C.c_double), ("abs_tol", C.c_double)]
+
+
+LM_CONVERGED = 1
+LM_MAX_ITERS = 2
+LM_STALLED = 3
+
 # name -> (restype, argtypes)
 _SIGS = {
+    "pa_trajectory_lm_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pa_trajectory_lm_solve": (C.c_int, [C.POINTER(TrajArgs), C.POINTER(LMParams)] + [C.c_void_p] * 7
+                               + [C.c_size_t, C.c_void_p]),
+    "pa_window_lm_solve": (C.c_int, [C.POINTER(TrajArgs), C.POINTER(LMParams), C.c_int] + [C.c_void_p] * 7
+                           + [C.c_size_t, C.c_void_p]),
+    "pa_window_pose_tick_reduce": (C.c_int, [C.POINTER(TrajArgs), C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pa_trajectory_linearize": (C.c_int, [C.POINTER(TrajArgs), C.c_void_p]),
     "pa_debug_trajectory_linearize": (C.c_int, [C.POINTER(TrajArgs), C.c_int, C.c_void_p, C.c_void_p]),
     "pa_last_error": (C.c_char_p, []),

@@ -193,6 +193,84 @@ def gn_step(lin: dict, *, T: int, L: int, lam: float = 0.0) -> dict:
     return out
 
 
+LM_DEFAULTS = dict(max_iters=30, lambda0=1e-3, lambda_up=10.0, lambda_down=10.0, lambda_min=1e-12, lambda_max=1e12,
+                   rel_tol=1e-6, abs_tol=1e-9)
+
+
+class LMPlan:
+    """Levenberg-Marquardt per trajectory on the device (pa_trajectory_lm_solve: what a GTSAM
+    LevenbergMarquardtOptimizer.optimize() call does for the reference's users) over `args`, `lin`
+    = prepare_trajectories(...) run with all three whitening sigmas and Jacobians.  Outputs and
+    workspace are allocated once, so `launch` (1 + 2 max_iters kernel launches, no host
+    synchronisation) can be captured in a HIP graph and replayed.  The state arrays `args`
+    points at (pose, vel, angvel) are updated in place to the final accepted state and `lin`
+    then holds the linearization there.  out: cost0, cost, lambda (T,) f64, iters, status (T,)
+    int32 (_lib.LM_CONVERGED / LM_MAX_ITERS / LM_STALLED), cost_hist (T, max_iters + 1) f64 (NaN
+    after a trajectory's stop).  Keywords: the fields of pa_lm_params (LM_DEFAULTS).
+    newest_pending: the window is the one the split tick's pre half leaves between ticks (frame
+    L-1 predicted, its keypoints not in yet): its projection factors stay out (pa_window_lm_solve)."""
+
+    def __init__(self, args, lin: dict, *, T: int, L: int, newest_pending: bool = False, **params):
+        unknown = set(params) - set(LM_DEFAULTS)
+        if unknown:
+            raise TypeError(f"LMPlan: unknown parameters {sorted(unknown)}")
+        if lin.get("j_proj") is None:
+            raise RuntimeError("lm_solve needs the Jacobians (prepare_trajectories with jacobians=True)")
+        if any(lin.get(k) is None for k in ("err_proj", "err_dyn", "err_cv")):
+            raise RuntimeError("lm_solve needs proj_sigmas, dyn_sigmas and cv_sigmas (the cost is whitened)")
+        p = dict(LM_DEFAULTS, **params)
+        self.params = _lib.LMParams(int(p["max_iters"]), *(float(p[k]) for k in (
+            "lambda0", "lambda_up", "lambda_down", "lambda_min", "lambda_max", "rel_tol", "abs_tol")))
+        dev = lin["r_proj"].device
+        self.args, self.lin, self.T, self.L, self.dev = args, lin, T, L, dev
+        self.max_iters = int(p["max_iters"])
+        self.newest_pending = bool(newest_pending)
+
+        def e(*shape, dtype=torch.float64):
+            return torch.empty(shape, dtype=dtype, device=dev)
+
+        self.out = {"cost0": e(T), "cost": e(T), "lambda": e(T), "iters": e(T, dtype=torch.int32),
+                    "status": e(T, dtype=torch.int32), "cost_hist": e(T, max(self.max_iters, 0) + 1)}
+        n = int(_lib.lib().pa_trajectory_lm_workspace(T, L, int(args.n_kp), self.max_iters))
+        self.ws = torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
+
+    def launch(self) -> None:
+        """One pa_trajectory_lm_solve on the device's current stream."""
+        o, p = self.out, _lib.ptr
+        with torch.cuda.device(self.dev):
+            tail = (p(o["cost0"]), p(o["cost"]), p(o["iters"]), p(o["status"]), p(o["lambda"]), p(o["cost_hist"]),
+                    p(self.ws), self.ws.numel(), _lib.stream_of(self.dev))
+            if self.newest_pending:
+                _lib.check(_lib.lib().pa_window_lm_solve(C.byref(self.args), C.byref(self.params), 1, *tail),
+                           "pa_window_lm_solve")
+            else:
+                _lib.check(_lib.lib().pa_trajectory_lm_solve(C.byref(self.args), C.byref(self.params), *tail),
+                           "pa_trajectory_lm_solve")
+
+
+def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: int, dt: float, proj_sigmas, dyn_sigmas,
+             cv_sigmas, nvalid: torch.Tensor | None = None, vel_frame: str = "world", camera_pose=None, H: int = 256,
+             W: int = 256, newest_pending: bool = False, **params) -> dict:
+    """Smoothed trajectories: Levenberg-Marquardt over all factors of T trajectories x L frames
+    from the keypoints `y` (device) and the initial state, on the device (pa_trajectory_lm_solve;
+    layouts as linearize_trajectories, the inputs are not modified).  Returns pose (T*L, 12),
+    vel, angvel (T*L, 3) at the final accepted state, cost0, cost, iters, status, lambda (T,),
+    cost_hist (T, max_iters + 1), and `lin`: the factor outputs at that state.  newest_pending: frame
+    L-1 has no keypoints yet and its projection factors stay out (pa_window_lm_solve).  **params:
+    max_iters, lambda0, lambda_up, lambda_down, lambda_min, lambda_max, rel_tol, abs_tol."""
+    dev = y.device
+    P, V, Wv = (_f64(a, dev).clone() for a in (poses, vels, angvels))  # updated in place: never the caller's
+    a, lin = prepare_trajectories(y, P, V, Wv, corners, K, T=T, L=L, dt=dt, vel_frame=vel_frame,
+                                  camera_pose=camera_pose, H=H, W=W, proj_sigmas=proj_sigmas, dyn_sigmas=dyn_sigmas,
+                                  cv_sigmas=cv_sigmas, nvalid=nvalid)
+    P, V, Wv = lin["_keep"][1:4]
+    plan = LMPlan(a, lin, T=T, L=L, newest_pending=newest_pending, **params)
+    plan.launch()
+    out = dict(plan.out)
+    out.update(pose=P, vel=V, angvel=Wv, lin=lin, _ws=plan.ws)
+    return out
+
+
 def window_advance(y_new: torch.Tensor, win: dict, *, dt: float, vel_frame: str = "world",
                    nvalid: torch.Tensor | None = None) -> None:
     """pa_window_advance on the device's current stream: every trajectory's window
@@ -239,6 +317,15 @@ def window_pose_tick_pre(args, ws: torch.Tensor, *, lam: float) -> None:
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().pa_window_pose_tick_pre(C.byref(args), float(lam), ws.data_ptr(), ws.numel(),
                                                       _lib.stream_of(dev)), "pa_window_pose_tick_pre")
+
+
+def window_pose_tick_reduce(args, ws: torch.Tensor, *, lam: float) -> None:
+    """pa_window_pose_tick_reduce on the device's current stream: the pre half's reduction alone,
+    from the factor outputs as they stand (no advance, no linearize)."""
+    dev = ws.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().pa_window_pose_tick_reduce(C.byref(args), float(lam), ws.data_ptr(), ws.numel(),
+                                                         _lib.stream_of(dev)), "pa_window_pose_tick_reduce")
 
 
 def window_pose_tick_post(args, y_new: torch.Tensor, ws: torch.Tensor, *, delta: torch.Tensor, info: torch.Tensor,

@@ -323,6 +323,39 @@ class StreamingPipeline:
                 self._enqueue_pose_pre()
         self.stream.synchronize()
 
+    def solve_window(self, max_iters: int = 20, **params) -> dict:
+        """Levenberg-Marquardt on the current window of every camera (pipeline.LMPlan,
+        pa_trajectory_lm_solve): the tick takes ONE fixed-lambda step per frame, which nothing
+        protects when the window is far from the truth (start-up from the guessed init_pose);
+        this iterates with accept / reject and adaptive damping until each camera's window has
+        converged.  Runs eagerly on the pipeline's stream, outside the captured tick graph (the
+        tick itself is unchanged), and updates the window in place.  Returns per camera: status
+        (_lib.LM_CONVERGED / LM_MAX_ITERS / LM_STALLED), cost0, cost, iters (numpy).  **params:
+        the other fields of pa_lm_params (pipeline.LM_DEFAULTS).
+        With pre_ahead the window between ticks is already the next tick's: advanced, its newest
+        frame predicted and without keypoints.  That frame's projection factors stay out of the
+        solve (pa_window_lm_solve, newest_pending: its dynamics factor alone holds it), and the
+        pre half's reduction is then redone on the solved window (pa_window_pose_tick_reduce:
+        the whole pre half would advance the window a second time).
+        Windows above 24 frames (pipeline.TICK_MAX_L, the cyclic-reduction solver's range) run
+        the four-launch tick but have no LM solve: ValueError."""
+        if not self.pose_L:
+            raise RuntimeError("solve_window() needs the pose stage (pose_window > 0)")
+        if self.pose_L > pipeline.TICK_MAX_L:
+            raise ValueError(f"solve_window(): pose_window {self.pose_L} > {pipeline.TICK_MAX_L}, the range of the "
+                             "device Levenberg-Marquardt solve (pa_trajectory_lm_solve)")
+        key = (int(max_iters), tuple(sorted(params.items())))
+        if getattr(self, "_lm_key", None) != key:
+            self._lm = pipeline.LMPlan(self.traj_args, self.lin, T=self.n, L=self.pose_L, max_iters=max_iters,
+                                       newest_pending=self.pre_ahead, **params)
+            self._lm_key = key
+        with torch.cuda.stream(self.stream):
+            self._lm.launch()
+            if self.pre_ahead:
+                pipeline.window_pose_tick_reduce(self.traj_args, self.tick_ws, lam=self.gn.lam)
+        self.stream.synchronize()
+        return {k: self._lm.out[k].cpu().numpy() for k in ("status", "cost0", "cost", "iters")}
+
     def window_state(self) -> dict:
         """Host copies of the window (y, pose, vel, angvel) after the last tick (pre_ahead: after
         the next tick's advance, whose newest keypoints are not in yet)."""
