@@ -1,0 +1,84 @@
+// The factor outputs of pa_trajectory_linearize (the output pointers of pa_traj_args,
+// include/perseus_amd.h), listed once: X(field, element type, elements per unit, unit), the unit
+// a projection (T*L*K of them) or a frame pair (T*(L-1)).  Everything that treats them as a set
+// -- the struct of the 14 pointers, the select between two sets, the T = 1 view of one
+// trajectory, the LM workspace's copy of the set with its null checks and its final copy
+// (lm.hip) -- expands this list, so a new output is added here (and to the public header and
+// _lib.py).  Every expansion is unrolled by the preprocessor: no table is indexed at run time.
+#pragma once
+#include "common.h"
+
+#define PA_FACTOR_OUTPUTS(X)       \
+  X(r_proj, double, 2, FU_PROJ)    \
+  X(j_proj, double, 12, FU_PROJ)   \
+  X(err_proj, double, 1, FU_PROJ)  \
+  X(status, int32_t, 1, FU_PROJ)   \
+  X(r_dyn, double, 6, FU_PAIR)     \
+  X(j_dyn0, double, 36, FU_PAIR)   \
+  X(j_dyn1, double, 18, FU_PAIR)   \
+  X(j_dyn2, double, 18, FU_PAIR)   \
+  X(j_dyn3, double, 36, FU_PAIR)   \
+  X(err_dyn, double, 1, FU_PAIR)   \
+  X(r_cv, double, 3, FU_PAIR)      \
+  X(j_cv0, double, 9, FU_PAIR)     \
+  X(j_cv1, double, 9, FU_PAIR)     \
+  X(err_cv, double, 1, FU_PAIR)
+
+namespace pa {
+
+enum FactorUnit { FU_PROJ, FU_PAIR };
+// units of kind u among np projections and nd frame pairs (u is a constant at every use)
+template <typename N>
+__host__ __device__ constexpr N factor_units(FactorUnit u, N np, N nd) {
+  return u == FU_PROJ ? np : nd;
+}
+
+struct FactorSet {
+#define PA_X(f, V, n, u) V* f;
+  PA_FACTOR_OUTPUTS(PA_X)
+#undef PA_X
+};
+
+// the set a pa_traj_args names
+__host__ __device__ __forceinline__ FactorSet factor_set(const pa_traj_args& ta) {
+  FactorSet s;
+#define PA_X(f, V, n, u) s.f = ta.f;
+  PA_FACTOR_OUTPUTS(PA_X)
+#undef PA_X
+  return s;
+}
+
+// b if w, else a: per pointer a select between two kernel-argument structs (uniform when w
+// is; an indexed copy, sets[w], would put both sets in scratch)
+__device__ __forceinline__ FactorSet factor_set_select(const FactorSet& a, const FactorSet& b, bool w) {
+  FactorSet s;
+#define PA_X(f, V, n, u) s.f = w ? b.f : a.f;
+  PA_FACTOR_OUTPUTS(PA_X)
+#undef PA_X
+  return s;
+}
+
+// trajectory t's factors: the arrays of a T = 1 problem start at its records.  The state
+// (y, pose, vel, angvel) is ta's, the factor outputs are s's (factor_set(ta): ta's own); a
+// null nvalid stays null, and so does a null output (err_*, the projection arrays at K = 0)
+// unless the caller knows that s has none (NULLS = false: no tests; lm_lin_kernel, which is
+// at the edge of its register budget).
+template <bool NULLS = true>
+__device__ __forceinline__ pa_traj_args traj_view(const pa_traj_args& ta, int t, const FactorSet s) {
+  const int L = ta.L, K = ta.n_kp;
+  const long f0 = (long)t * L, p0 = f0 * K, d0 = (long)t * (L - 1);
+  auto off = [](auto* q, long n) { return q ? q + n : q; };
+  pa_traj_args a1 = ta;
+  a1.T = 1;
+  a1.y = ta.y + f0 * 2 * K;
+  a1.pose = ta.pose + f0 * 12;
+  a1.vel = ta.vel + f0 * 3;
+  a1.angvel = ta.angvel + f0 * 3;
+#define PA_X(f, V, n, u) a1.f = NULLS ? off(s.f, factor_units(u, p0, d0) * n) : s.f + factor_units(u, p0, d0) * n;
+  PA_FACTOR_OUTPUTS(PA_X)
+#undef PA_X
+  a1.nvalid = off(ta.nvalid, (long)t);
+  return a1;
+}
+
+}  // namespace pa

@@ -1,10 +1,11 @@
 // Device code of the smoother factors (factors.hip): the GTSAM 4.2 geometry, the three
 // factors' residual / Jacobian evaluations and the config-3 trajectory units, shared with
-// the fused streaming pose tick (gn.hip, pa_window_pose_tick).
+// the fused streaming pose tick (pose_tick.hip, pa_window_pose_tick) and the LM solve (lm.hip).
 #pragma once
 #include <cmath>
 
 #include "common.h"
+#include "factor_outputs.h"
 
 namespace pa {
 
@@ -815,6 +816,25 @@ __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, do
   if (ts) {
     __builtin_amdgcn_s_waitcnt(0);
     traj_stamp(ts, 7);
+  }
+}
+
+// One trajectory's factors by one workgroup of TICK_LIN_W waves (pose_tick_lin_kernel,
+// lm_lin_kernel), a1 its T = 1 view (traj_view): waves 0-1 its L-1 dynamics factors
+// (traj_dyn_block), then one wave per 256 projection factors and one for the
+// constant-velocity ones (traj_unit_wave).  st: LIN_STAGE doubles of LDS.  Every wave of the
+// workgroup calls it (one LDS barrier inside).
+constexpr int TICK_LIN_W = 6;
+constexpr int LIN_STAGE = trj::STAGE + 4 * trj::UNIT;
+static_assert(LIN_STAGE * 8 <= 96 * 1024, "factor staging");
+__device__ __forceinline__ void traj_lin_block(const pa_traj_args& a1, double* st) {
+  const int wv = threadIdx.x >> 6;
+  const int wp = (a1.L * a1.n_kp + 64 * trj::PPW - 1) / (64 * trj::PPW);  // projection units (<= 2); unit wp: constant velocity
+  if (wv < 2) {
+    traj_dyn_block(a1, 0, st, nullptr);  // (its one LDS barrier is matched by every other wave's below)
+  } else {
+    if (wv - 2 <= wp) traj_unit_wave(a1, wv - 2, st + trj::STAGE + (wv - 2) * trj::UNIT, nullptr);
+    lds_barrier();
   }
 }
 

@@ -30,19 +30,21 @@ MARGIN = 1e-6  # decisions the reference takes with a smaller |C' - C| / C are n
 # damping, down to 1e-7, hold; every other case stays below 4.1e-13.  The cost figure is set at
 # the noise floor, C ~ 1e-10: its residuals of ~1e-5 px are differences of ~128 px quantities,
 # eps * 128 / 1e-5 = 2.8e-9 relative each; above the floor the measured deviation is 1e-16 .. 1e-11.)
+# The n_kp = 5 parity case (lm_step_kernel's general instantiation), measured the same way: state
+# 4.82e-13, cost_hist 1.72e-9 relative (at the same floor), inside the bounds above.
 STATE_ATOL = 7.76e-11
 HIST_RTOL = 1.9e-8
 ROT_TOL, TRA_TOL = 1e-4, 1e-5  # test_streaming_pose_gpu.test_pose_tracks_known_trajectory
 SIG = lm_ref.SIGMAS
 
 
-def _dev(pr, T, L, params, nvalid=None, pending=False):
+def _dev(pr, T, L, params, nvalid=None, pending=False, corners=None):
     """pipeline.lm_solve on a lm_ref problem; numpy outputs."""
     nv = None if nvalid is None else torch.as_tensor(np.asarray(nvalid, np.int32), device="cuda")
     out = pipeline.lm_solve(torch.as_tensor(pr["y"], device="cuda"), pr["pose"], pr["vel"], pr["angvel"],
-                            synth.CUBE_CORNERS, synth.CAMERA_K, T=T, L=L, dt=lm_ref.DT, proj_sigmas=[SIG["proj"]] * 2,
-                            dyn_sigmas=[SIG["dyn"]] * 6, cv_sigmas=[SIG["cv"]] * 3, nvalid=nv, newest_pending=pending,
-                            **params)
+                            synth.CUBE_CORNERS if corners is None else corners, synth.CAMERA_K, T=T, L=L, dt=lm_ref.DT,
+                            proj_sigmas=[SIG["proj"]] * 2, dyn_sigmas=[SIG["dyn"]] * 6, cv_sigmas=[SIG["cv"]] * 3,
+                            nvalid=nv, newest_pending=pending, **params)
     torch.cuda.synchronize()
     res = {k: out[k].cpu().numpy() for k in ("pose", "vel", "angvel", "cost0", "cost", "iters", "status", "lambda",
                                              "cost_hist")}
@@ -50,8 +52,9 @@ def _dev(pr, T, L, params, nvalid=None, pending=False):
     return res
 
 
-def _ref(pr, T, L, params, nvalid=None, pending=False):
-    return lm_ref.solve(pr["y"], pr["pose"], pr["vel"], pr["angvel"], T, L, params, nvalid=nvalid, pending=pending)
+def _ref(pr, T, L, params, nvalid=None, pending=False, corners=None):
+    return lm_ref.solve(pr["y"], pr["pose"], pr["vel"], pr["angvel"], T, L, params, nvalid=nvalid, pending=pending,
+                        corners=corners)
 
 
 def _deviation(dev, ref):
@@ -96,15 +99,29 @@ def test_decisions_match_reference(T, L):
     floor of its f32 keypoints early then improves by 1e-8 relative steps), and a second solve of
     as many iterations as EVERY trajectory decides with that margin is compared in full: iters,
     status, lambda, cost_hist and the final state."""
+    _check_decisions(lm_ref.problem(T, L, 0.8), T, L)
+
+
+def test_decisions_match_reference_five_keypoints():
+    """n_kp = 5 (the first five cube corners): lm_step_kernel's general instantiation, which every
+    other case of this file (8 corners) leaves out.  The comparison of test_decisions_match_reference;
+    the reference decides 8 and 6 leading iterations with the margin, trajectory 0 rejecting its first
+    five steps and trajectory 1 accepting its first seven."""
+    T, L = 2, 6
     pr = lm_ref.problem(T, L, 0.8)
-    ref = _ref(pr, T, L, PARITY)
+    pr["y"] = np.ascontiguousarray(pr["y"][:, :10])
+    _check_decisions(pr, T, L, corners=synth.CUBE_CORNERS[:5])
+
+
+def _check_decisions(pr, T, L, corners=None):
+    ref = _ref(pr, T, L, PARITY, corners=corners)
     nok = _well_defined(ref, T)
     dec = [[r["accept"] for r in log] for log in ref["log"]]
     print("reference decisions:", dec, "well defined:", nok)
     assert min(nok) >= 5  # (the seeds' figure; a change of the problem that lowers it needs another seed)
     assert any(not a for d, n in zip(dec, nok) for a in d[:n]), "no reject among the compared decisions"
     assert any(a for d, n in zip(dec, nok) for a in d[:n]), "no accept among the compared decisions"
-    dev = _dev(pr, T, L, PARITY)
+    dev = _dev(pr, T, L, PARITY, corners=corners)
     for t in range(T):
         n = nok[t]
         h, g = dev["cost_hist"][t, :n + 1], ref["cost_hist"][t, :n + 1]
@@ -114,10 +131,10 @@ def test_decisions_match_reference(T, L):
         np.testing.assert_array_equal(np.diff(h) < 0, dec[t][:n])  # the same accepts and rejects
     m = min(nok)
     short = dict(PARITY, max_iters=m)
-    ref_m = _ref(pr, T, L, short)
+    ref_m = _ref(pr, T, L, short, corners=corners)
     for t in range(T):
         assert all(r["margin"] >= MARGIN for r in ref_m["log"][t])  # every compared decision, on the reference alone
-    _assert_matches(_dev(pr, T, L, short), ref_m, T, f"T={T} L={L}, {m} iterations")
+    _assert_matches(_dev(pr, T, L, short, corners=corners), ref_m, T, f"T={T} L={L}, {m} iterations")
     for t in range(T):  # trajectories decided with the margin throughout: the 8-iteration solve in full
         if nok[t] == PARITY["max_iters"]:
             one = {k: (v[t * L:(t + 1) * L] if k in ("pose", "vel", "angvel") else v[t:t + 1])

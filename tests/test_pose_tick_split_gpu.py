@@ -1,4 +1,4 @@
-"""pa_window_pose_tick_pre + _post (the split streaming tick, csrc/gn.hip) against
+"""pa_window_pose_tick_pre + _post (the split streaming tick, csrc/pose_tick.hip) against
 pa_window_pose_tick (the fused tick, itself bit-identical to the four separate calls) at every
 level structure of the ROOT-order cyclic reduction: L = 2 .. 24 (even and odd level counts,
 the n = 3 -> 2 -> 1 tail), n_kp = 8 (the RP = 34 instance) and 16 (the general one), windows
