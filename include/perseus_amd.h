@@ -261,6 +261,37 @@ int pa_trajectory_gn_step(int T, int L, int n_kp, const double* r_proj, const do
                           const double* j_cv0, const double* j_cv1, double lambda, double* D, double* E, double* g,
                           double* delta, int32_t* info, void* ws, size_t ws_bytes, void* stream);
 
+/* Marginal covariances of the same graph (what gtsam.Marginals(graph, values)
+ * .marginalCovariance(key) gives the reference's users on the host), per trajectory, from the
+ * same WHITENED factors in the same order as pa_trajectory_gn_step (same layouts, same null
+ * rules; projection factors with status != 0 are skipped):
+ *   Sigma = (J^T J + lambda I)^-1,  lambda >= 0,
+ * lambda I being an isotropic prior of precision lambda on every variable.  Outputs:
+ * cov (T*L, 12, 12) the diagonal blocks Sigma_{l,l}, the marginal covariance of frame l's
+ * [pose tangent (6, [omega; v]) | angular velocity (3) | velocity (3)] in the tangent space of
+ * pa_window_retract's chart (a right perturbation, GTSAM's Pose3 convention); cross
+ * (T*(L-1), 12, 12) or NULL, Sigma_{l,l+1} row-major with frame l on rows and frame l+1 on
+ * columns (E's convention; requires cov); cov_newest (T, 12, 12) or NULL, Sigma_{L-1,L-1}
+ * alone, bit for bit cov's last block (given without cov, only the forward elimination runs);
+ * at least one of cov / cov_newest.  Every block is exactly symmetric.  info (T, required) = 0
+ * or the 1-based frame whose pivot block of the top-down block elimination was not positive
+ * definite; every output block of that trajectory is then NaN.
+ * lambda = 0 has no special case: on a full window the last frame's angular velocity is in no
+ * factor, so lambda = 0 fails at frame L (as pa_trajectory_gn_step does); pass a small lambda
+ * (for example 1e-9) for the undamped Gauss-Newton covariance -- the unconstrained variable
+ * is decoupled and gets variance 1 / lambda.  Partly filled windows (nvalid < L) and a pending
+ * newest frame (status 3) are singular at lambda = 0 for a real reason (9 equations for 12
+ * unknowns per frame without keypoints) and need a lambda of the streaming tick's order (1e-2).
+ * T >= 0 (0 is a no-op), L >= 2, 0 <= n_kp <= 16; everything else returns PA_EINVAL before any
+ * launch.  One launch on `stream`, no host synchronisation (capturable).
+ * ws: pa_trajectory_marginals_workspace bytes. */
+size_t pa_trajectory_marginals_workspace(int T, int L);
+int pa_trajectory_marginals(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                            const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                            const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
+                            const double* j_cv0, const double* j_cv1, double lambda, double* cov, double* cross,
+                            double* cov_newest, int32_t* info, void* ws, size_t ws_bytes, void* stream);
+
 /* Levenberg-Marquardt over the same graph (what GTSAM's LevenbergMarquardtOptimizer::optimize
  * does on the host for the reference's users), per trajectory and independently, all on the
  * device: 1 + 2 max_iters launches on `stream`, no host synchronisation (capturable).

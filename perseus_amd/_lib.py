@@ -92,6 +92,9 @@ _SIGS = {
     "pa_trajectory_gn_workspace": (C.c_size_t, [C.c_int, C.c_int]),
     "pa_trajectory_gn_step": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_double]
                               + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
+    "pa_trajectory_marginals_workspace": (C.c_size_t, [C.c_int, C.c_int]),
+    "pa_trajectory_marginals": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_double]
+                                + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
     "pa_window_advance": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double, C.c_int,
                                                                                      C.c_void_p]),
     "pa_window_advance_n": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double, C.c_int,

@@ -193,6 +193,67 @@ def gn_step(lin: dict, *, T: int, L: int, lam: float = 0.0) -> dict:
     return out
 
 
+class MarginalsPlan:
+    """Marginal covariances of every trajectory (pa_trajectory_marginals: what
+    gtsam.Marginals(graph, values).marginalCovariance(key) gives on the host) over `lin` = the
+    whitened factor outputs GNPlan takes: Sigma = (J^T J + lam I)^-1 per trajectory.  Outputs
+    and workspace are allocated once, so `launch` can be captured in a HIP graph and replayed.
+    out: info (T,) int32 (0, or the 1-based frame of a failed pivot block: that trajectory's
+    blocks are NaN); full=True: cov (T*L,12,12), the marginal covariance of each frame's
+    [pose (6, right perturbation, [omega; v]) | angvel (3) | vel (3)]; cross=True (needs full):
+    cross (T*(L-1),12,12) = Sigma_{l,l+1}, frame l on rows; newest=True: cov_newest (T,12,12),
+    bit for bit cov's last block per trajectory (alone, only the forward elimination runs).
+    lam = 0 fails on a full window (the last frame's angular velocity is in no factor): pass a
+    small lam (1e-9) for the undamped covariance."""
+
+    def __init__(self, lin: dict, *, T: int, L: int, lam: float, full: bool = True, cross: bool = False,
+                 newest: bool = False):
+        if lin.get("j_proj") is None:
+            raise RuntimeError("marginals needs the Jacobians (linearize with jacobians=True)")
+        if not (full or newest):
+            raise ValueError("MarginalsPlan: nothing to compute (full=False and newest=False)")
+        if cross and not full:
+            raise ValueError("MarginalsPlan: cross=True needs full=True")
+        dev = lin["r_proj"].device
+        self.T, self.L, self.lam, self.lin, self.dev = T, L, float(lam), lin, dev
+        self.n_kp = lin["r_proj"].shape[0] // (T * L) if T * L else 0
+
+        def e(*shape, dtype=torch.float64):
+            return torch.empty(shape, dtype=dtype, device=dev)
+
+        self.out = {"info": e(T, dtype=torch.int32)}
+        if full:
+            self.out["cov"] = e(T * L, 12, 12)
+        if cross:
+            self.out["cross"] = e(T * max(L - 1, 0), 12, 12)
+        if newest:
+            self.out["cov_newest"] = e(T, 12, 12)
+        n = int(_lib.lib().pa_trajectory_marginals_workspace(T, L))
+        self.ws = torch.empty(max(n, 8), dtype=torch.uint8, device=dev)
+
+    def launch(self) -> None:
+        """One pa_trajectory_marginals on the device's current stream."""
+        lin, out, p = self.lin, self.out, _lib.ptr
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().pa_trajectory_marginals(
+                self.T, self.L, self.n_kp, p(lin["r_proj"]), p(lin["j_proj"]), p(lin.get("status")), p(lin["r_dyn"]),
+                p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]), p(lin["r_cv"]),
+                p(lin["j_cv0"]), p(lin["j_cv1"]), self.lam, p(out.get("cov")), p(out.get("cross")),
+                p(out.get("cov_newest")), p(out["info"]), p(self.ws), self.ws.numel(), _lib.stream_of(self.dev)),
+                "pa_trajectory_marginals")
+
+
+def marginals(lin: dict, *, T: int, L: int, lam: float, cross: bool = False) -> dict:
+    """Marginal covariances on the device (pa_trajectory_marginals, MarginalsPlan): cov
+    (T*L,12,12) = the diagonal blocks of (J^T J + lam I)^-1 over the whitened factors `lin`, info
+    (T,) int32 (0 = computed) and, with cross=True, cross (T*(L-1),12,12) = Sigma_{l,l+1}."""
+    plan = MarginalsPlan(lin, T=T, L=L, lam=lam, cross=cross)
+    plan.launch()
+    out = dict(plan.out)
+    out["_ws"] = plan.ws
+    return out
+
+
 LM_DEFAULTS = dict(max_iters=30, lambda0=1e-3, lambda_up=10.0, lambda_down=10.0, lambda_min=1e-12, lambda_max=1e12,
                    rel_tol=1e-6, abs_tol=1e-9)
 
@@ -250,14 +311,18 @@ class LMPlan:
 
 def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: int, dt: float, proj_sigmas, dyn_sigmas,
              cv_sigmas, nvalid: torch.Tensor | None = None, vel_frame: str = "world", camera_pose=None, H: int = 256,
-             W: int = 256, newest_pending: bool = False, **params) -> dict:
+             W: int = 256, newest_pending: bool = False, covariance: bool = False, cov_lambda: float = 1e-9,
+             **params) -> dict:
     """Smoothed trajectories: Levenberg-Marquardt over all factors of T trajectories x L frames
     from the keypoints `y` (device) and the initial state, on the device (pa_trajectory_lm_solve;
     layouts as linearize_trajectories, the inputs are not modified).  Returns pose (T*L, 12),
     vel, angvel (T*L, 3) at the final accepted state, cost0, cost, iters, status, lambda (T,),
     cost_hist (T, max_iters + 1), and `lin`: the factor outputs at that state.  newest_pending: frame
     L-1 has no keypoints yet and its projection factors stay out (pa_window_lm_solve).  **params:
-    max_iters, lambda0, lambda_up, lambda_down, lambda_min, lambda_max, rel_tol, abs_tol."""
+    max_iters, lambda0, lambda_up, lambda_down, lambda_min, lambda_max, rel_tol, abs_tol.
+    covariance=True: also cov (T*L, 12, 12) and cov_info (T,), the marginal covariances
+    (pipeline.marginals) of the linearization the solve leaves at the final state, with
+    lam = cov_lambda (partly filled or pending windows need about 1e-2, see MarginalsPlan)."""
     dev = y.device
     P, V, Wv = (_f64(a, dev).clone() for a in (poses, vels, angvels))  # updated in place: never the caller's
     a, lin = prepare_trajectories(y, P, V, Wv, corners, K, T=T, L=L, dt=dt, vel_frame=vel_frame,
@@ -268,6 +333,9 @@ def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: in
     plan.launch()
     out = dict(plan.out)
     out.update(pose=P, vel=V, angvel=Wv, lin=lin, _ws=plan.ws)
+    if covariance:
+        m = marginals(lin, T=T, L=L, lam=cov_lambda)
+        out.update(cov=m["cov"], cov_info=m["info"], _cov_ws=m["_ws"])
     return out
 
 

@@ -362,6 +362,28 @@ class StreamingPipeline:
         self.stream.synchronize()
         return {k: v.cpu().numpy().copy() for k, v in self.win.items()}
 
+    def window_covariance(self, lam: float | None = None) -> dict:
+        """Marginal covariance of every frame of every camera's window (pipeline.MarginalsPlan,
+        pa_trajectory_marginals): cov (n, L, 12, 12), Sigma = (J^T J + lam I)^-1 restricted to
+        each frame's [pose (6, right perturbation, [omega; v]) | angvel (3) | vel (3)], and info
+        (n,) int32 (0 = computed), as numpy.  Reads the factor outputs (self.lin) as they stand:
+        the last tick's linearization (pre_ahead: the next tick's pre half's, so between ticks
+        frame L-1 is the predicted one, its projection factors are out (status 3) and its
+        covariance is the prediction's, as window_state()).  lam defaults to the tick's; a window
+        that has not filled yet needs a lam of that order.  Runs eagerly on the pipeline's
+        stream, outside the captured tick graph."""
+        if not self.pose_L:
+            raise RuntimeError("window_covariance() needs the pose stage (pose_window > 0)")
+        lam = self.gn.lam if lam is None else float(lam)
+        if getattr(self, "_marg", None) is None:
+            self._marg = pipeline.MarginalsPlan(self.lin, T=self.n, L=self.pose_L, lam=lam)
+        self._marg.lam = lam
+        with torch.cuda.stream(self.stream):
+            self._marg.launch()
+        self.stream.synchronize()
+        return {"cov": self._marg.out["cov"].view(self.n, self.pose_L, 12, 12).cpu().numpy().copy(),
+                "info": self._marg.out["info"].cpu().numpy().copy()}
+
     def stage(self, rgb: np.ndarray, depth: np.ndarray | None = None) -> None:
         """Copy one tick of camera frames (n, Hs, Ws, 3) uint8 + (n, Hs, Ws) f32 metres
         into the pinned staging buffers (centre crop only when host_crop).  An RGB model
