@@ -38,6 +38,10 @@ extern "C" {
 #define PA_VEL_WORLD 0 /* factors.py:41 vel_frame="world" */
 #define PA_VEL_BODY 1  /* vel_frame="body"                */
 
+#define PA_ROBUST_NONE 0   /* plain Gaussian noise model: err = 0.5 |r_w|^2            */
+#define PA_ROBUST_HUBER 1  /* noiseModel::Robust(mEstimator::Huber(k), Diagonal)       */
+#define PA_ROBUST_CAUCHY 2 /* noiseModel::Robust(mEstimator::Cauchy(k), Diagonal)      */
+
 const char* pa_last_error(void);
 const char* pa_version(void);
 
@@ -191,6 +195,27 @@ int pa_proj_linearize(int n, const double* tbody_dev, const double* pb_dev, cons
                       const double* inv_sigma_dev, double* r_dev, double* j_dev, double* err_dev,
                       int32_t* status_dev, void* stream);
 
+/* Robust noise models on the projection factor (GTSAM's noiseModel::Robust over a diagonal
+ * model; the keypoints come from a CNN, and one occluded corner is tens of pixels off).  With
+ * the whitened residual r_w = r * inv_sigma (unit sigma when inv_sigma is NULL), the whitened
+ * Jacobian J_w, n = |r_w|_2 and k > 0 in whitened units:
+ *   PA_ROBUST_HUBER   w = 1 if n <= k, else k / n;   rho = n^2 / 2 if n <= k, else k (n - k / 2)
+ *   PA_ROBUST_CAUCHY  w = 1 / (1 + n^2 / k^2);       rho = (k^2 / 2) log1p(n^2 / k^2)
+ * the outputs are r = sqrt(w) r_w, J = sqrt(w) J_w (Robust::WhitenSystem) and err = rho, NOT
+ * 0.5 |r_w|^2.  status is unchanged: cheirality still gives NaN and status 1 (and in
+ * pa_trajectory_linearize frames outside nvalid zeros and status 2).  Everything that consumes
+ * the outputs (pa_trajectory_gn_step, pa_trajectory_marginals, the Levenberg-Marquardt cost,
+ * the streaming ticks) then does iteratively reweighted least squares unchanged, without a
+ * second-order (Triggs) term, as GTSAM does.  PA_ROBUST_NONE: the plain factor, bit for bit;
+ * k is then ignored.  A kind outside the three, or a kind != PA_ROBUST_NONE with k not a
+ * positive finite number, returns PA_EINVAL before any launch (every entry point that takes
+ * the kind checks it the same way).
+ * pa_proj_linearize_robust: pa_proj_linearize with the noise model's robust part. */
+int pa_proj_linearize_robust(int n, const double* tbody_dev, const double* pb_dev, const double* z_dev,
+                             const double* k_dev, int k_stride, const double* tcam_dev, int tcam_stride,
+                             const double* inv_sigma_dev, int robust_kind, double robust_k, double* r_dev,
+                             double* j_dev, double* err_dev, int32_t* status_dev, void* stream);
+
 /* PoseDynamicsFactor (factors.py:54-142): r = Log((T1 Exp(dt[w; v_b]))^-1 T2),
  * v_b = R1^T v if vel_frame == PA_VEL_WORLD.  J0 6x6 (pose1), J1 6x3 (ang_vel1),
  * J2 6x3 (vel1), J3 6x6 (pose2); any J pointer may be NULL (error-only). */
@@ -215,7 +240,13 @@ int pa_cv_linearize(int n, const double* v1_dev, const double* v2_dev, const dou
  * nvalid (may be NULL): per trajectory the number of trailing frames that hold a real
  * measurement (the streaming window before it has filled, pa_window_advance_n); the
  * projection factors of frames l < L - nvalid[t] get status 2 and r = J = err = 0, so the
- * GN step skips them. */
+ * GN step skips them.
+ * robust_proj / robust_proj_k: the projection factors' robust noise model (see
+ * pa_proj_linearize_robust: r_proj and j_proj are then sqrt(w)-scaled and err_proj is rho).  A
+ * zero-initialised pair means none, so callers that never set them keep the plain factors.
+ * Every entry point that takes a pa_traj_args (pa_trajectory_linearize, pa_trajectory_lm_solve,
+ * pa_window_lm_solve, pa_window_pose_tick and its _pre / _post / _reduce forms) honours them
+ * and rejects a bad pair with PA_EINVAL. */
 typedef struct pa_traj_args {
   int T, L, n_kp, H, W;
   const float* y;          /* (T*L, 2K) normalized keypoints */
@@ -235,6 +266,8 @@ typedef struct pa_traj_args {
   double *r_dyn, *j_dyn0, *j_dyn1, *j_dyn2, *j_dyn3, *err_dyn;
   double *r_cv, *j_cv0, *j_cv1, *err_cv;
   const int32_t* nvalid;   /* (T) or NULL: frames with measurements, from the window's end */
+  int robust_proj;         /* PA_ROBUST_*: the projection factors' robust noise model (0 = none) */
+  double robust_proj_k;    /* its k > 0, in whitened units (host scalar; ignored for PA_ROBUST_NONE) */
 } pa_traj_args;
 
 int pa_trajectory_linearize(const pa_traj_args* args, void* stream);
@@ -300,7 +333,8 @@ int pa_trajectory_marginals(int T, int L, int n_kp, const double* r_proj, const 
  * nvalid is honoured.  args->pose / vel / angvel are updated IN PLACE to the final accepted
  * state, and on return the factor outputs hold the linearization at that state.
  *   1. C = sum of err (0.5 |r_w|^2) over the dynamics and constant-velocity factors and the
- *      projection factors with status 0 at the state x; lambda = lambda0; cost0 = cost_hist[0] = C.
+ *      projection factors with status 0 at the state x (with args->robust_proj their err is the
+ *      m-estimator's rho, so C is the robust cost); lambda = lambda0; cost0 = cost_hist[0] = C.
  *   2. iteration k = 1..max_iters: (J^T J + lambda I) delta = -J^T r (pa_trajectory_gn_step's
  *      system).  A failed pivot rejects the step.  Else x' = retract(x, delta) (pa_window_retract's
  *      arithmetic), C' = the cost at x'; x' is rejected if a projection factor with status 0 at x

@@ -31,7 +31,8 @@ class TrajArgs(C.Structure):
                 ("isig_cv", C.c_void_p), ("r_proj", C.c_void_p), ("j_proj", C.c_void_p), ("err_proj", C.c_void_p),
                 ("status", C.c_void_p), ("r_dyn", C.c_void_p), ("j_dyn0", C.c_void_p), ("j_dyn1", C.c_void_p),
                 ("j_dyn2", C.c_void_p), ("j_dyn3", C.c_void_p), ("err_dyn", C.c_void_p), ("r_cv", C.c_void_p),
-                ("j_cv0", C.c_void_p), ("j_cv1", C.c_void_p), ("err_cv", C.c_void_p), ("nvalid", C.c_void_p)]
+                ("j_cv0", C.c_void_p), ("j_cv1", C.c_void_p), ("err_cv", C.c_void_p), ("nvalid", C.c_void_p),
+                ("robust_proj", C.c_int), ("robust_proj_k", C.c_double)]
 
 
 class LMParams(C.Structure):
@@ -115,6 +116,9 @@ _SIGS = {
     "pa_proj_linearize": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "pa_proj_linearize_robust": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pa_dyn_linearize": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -144,6 +148,23 @@ def precision_code(name: str) -> int:
 
 VEL_WORLD = 0
 VEL_BODY = 1
+
+ROBUST_NONE = 0
+ROBUST_HUBER = 1
+ROBUST_CAUCHY = 2
+ROBUST = {"huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY}
+
+
+def robust_code(robust) -> tuple:
+    """(PA_ROBUST_* kind, k) of a projection noise model's robust part: None (plain), a
+    ("huber" | "cauchy", k) pair, or an object with `.kind` and `.k` (smoother.noiseModel.mEstimator)."""
+    if robust is None:
+        return ROBUST_NONE, 0.0
+    kind, k = (robust.kind, robust.k) if hasattr(robust, "kind") else robust
+    try:
+        return ROBUST[kind], float(k)
+    except KeyError:
+        raise ValueError(f"robust kind must be one of {sorted(ROBUST)}, got {kind!r}") from None
 
 
 def lib_path() -> str:

@@ -6,6 +6,8 @@
 // (lm.hip) -- expands this list, so a new output is added here (and to the public header and
 // _lib.py).  Every expansion is unrolled by the preprocessor: no table is indexed at run time.
 #pragma once
+#include <cmath>
+
 #include "common.h"
 
 #define PA_FACTOR_OUTPUTS(X)       \
@@ -25,6 +27,20 @@
   X(err_cv, double, 1, FU_PAIR)
 
 namespace pa {
+
+// The robust noise model's arguments (include/perseus_amd.h, pa_proj_linearize_robust), checked
+// the same way by every entry point that takes them: `kind` / `k` name the caller's fields
+// (robust_proj / robust_proj_k of a pa_traj_args).  k is not looked at for PA_ROBUST_NONE.
+inline int robust_check(int kind, double k, const char* who, const char* kind_name, const char* k_name) {
+  PA_CHECK(kind == PA_ROBUST_NONE || kind == PA_ROBUST_HUBER || kind == PA_ROBUST_CAUCHY,
+           "%s: %s %d is not PA_ROBUST_NONE (0), PA_ROBUST_HUBER (1) or PA_ROBUST_CAUCHY (2)", who, kind_name, kind);
+  PA_CHECK(kind == PA_ROBUST_NONE || (k > 0.0 && k < INFINITY), "%s: %s %g must be a positive finite number (%s %d)",
+           who, k_name, k, kind_name, kind);
+  return PA_OK;
+}
+inline int robust_check(const pa_traj_args& ta, const char* who) {
+  return robust_check(ta.robust_proj, ta.robust_proj_k, who, "robust_proj", "robust_proj_k");
+}
 
 enum FactorUnit { FU_PROJ, FU_PAIR };
 // units of kind u among np projections and nd frame pairs (u is a constant at every use)

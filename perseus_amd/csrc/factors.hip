@@ -40,18 +40,20 @@ __global__ __launch_bounds__(64) void cv_kernel(int n, const double* __restrict_
          err ? err + u : nullptr);
 }
 
+// RB: with the robust noise models (pa_proj_linearize_robust with a kind); false: the plain factor
+template <bool RB>
 __global__ __launch_bounds__(64) void proj_kernel(int n, const double* __restrict__ Tb, const double* __restrict__ pbp,
                                                   const double* __restrict__ zp, const double* __restrict__ Kp,
                                                   int k_stride, const double* __restrict__ Tcp, int tc_stride,
-                                                  const double* __restrict__ isig, double* __restrict__ r_out,
-                                                  double* __restrict__ J, double* __restrict__ err,
-                                                  int32_t* __restrict__ status) {
+                                                  const double* __restrict__ isig, int robust, double rk,
+                                                  double* __restrict__ r_out, double* __restrict__ J,
+                                                  double* __restrict__ err, int32_t* __restrict__ status) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= n) return;
   const size_t u = i;
-  proj_one(Tb + u * 12, load3(pbp + u * 3), zp[u * 2], zp[u * 2 + 1], Kp + u * k_stride,
-           Tcp ? Tcp + u * tc_stride : nullptr, isig, r_out + u * 2, J ? J + u * 12 : nullptr, err ? err + u : nullptr,
-           status ? status + u : nullptr);
+  proj_one<RB>(Tb + u * 12, load3(pbp + u * 3), zp[u * 2], zp[u * 2 + 1], Kp + u * k_stride,
+           Tcp ? Tcp + u * tc_stride : nullptr, isig, robust, rk, r_out + u * 2, J ? J + u * 12 : nullptr,
+           err ? err + u : nullptr, status ? status + u : nullptr);
 }
 
 // one launch, the dynamics workgroups dispatched first: they hold the longest per-lane
@@ -67,6 +69,8 @@ __global__ __launch_bounds__(64) void proj_kernel(int n, const double* __restric
 // projection factors per lane: 14.7 us.  Three waves per SIMD does not fit (~220 VGPRs).
 // mode (pa_debug_trajectory_linearize, timing only): 1 = dynamics workgroups only,
 // 2 = projection / constant-velocity workgroups only
+// RB: the projection factors carry a robust noise model (a.robust_proj; chosen on the host)
+template <bool RB>
 __global__ __launch_bounds__(128, 2) void traj_all_kernel(pa_traj_args a, int mode, unsigned long long* ts) {
   __shared__ __attribute__((aligned(16))) double st[trj::STAGE];
   const long wd = ((long)a.T * (a.L - 1) + 63) / 64;
@@ -77,7 +81,7 @@ __global__ __launch_bounds__(128, 2) void traj_all_kernel(pa_traj_args a, int mo
     return;
   } else {
     const int wv = threadIdx.x >> 6;
-    traj_unit_wave(a, 2 * ((long)blockIdx.x - wd) + wv, st + wv * trj::UNIT, ts);
+    traj_unit_wave<RB>(a, 2 * ((long)blockIdx.x - wd) + wv, st + wv * trj::UNIT, ts);
   }
 }
 
@@ -164,6 +168,7 @@ int pa_cv_linearize(int n, const double* v1, const double* v2, const double* inv
 
 int pa_debug_trajectory_linearize(const pa_traj_args* a, int mode, unsigned long long* trace, void* stream) {
   PA_CHECK(a, "null args");
+  if (const int rc = pa::robust_check(*a, "trajectory linearize")) return rc;
   PA_CHECK(a->T >= 0 && a->L >= 1 && a->n_kp >= 1, "T=%d L=%d n_kp=%d", a->T, a->L, a->n_kp);
   if (a->T == 0) return PA_OK;
   PA_CHECK(a->y && a->pose && a->vel && a->angvel && a->corners && a->K, "null input pointer");
@@ -171,8 +176,9 @@ int pa_debug_trajectory_linearize(const pa_traj_args* a, int mode, unsigned long
   PA_CHECK(a->vel_frame == PA_VEL_WORLD || a->vel_frame == PA_VEL_BODY, "vel_frame must be 'world' or 'body'.");
   const long np = (long)a->T * a->L * a->n_kp, nd = (long)a->T * (a->L - 1);
   const long units = (np + 64 * pa::trj::PPW - 1) / (64 * pa::trj::PPW) + (nd + 63) / 64;  // projection | const-vel, two per workgroup
-  hipLaunchKernelGGL(pa::traj_all_kernel, dim3((unsigned)((nd + 63) / 64 + (units + 1) / 2)), dim3(128), 0,
-                     (hipStream_t)stream, *a, mode, trace);
+  const auto kernel = a->robust_proj == PA_ROBUST_NONE ? pa::traj_all_kernel<false> : pa::traj_all_kernel<true>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((nd + 63) / 64 + (units + 1) / 2)), dim3(128), 0, (hipStream_t)stream, *a,
+                     mode, trace);
   PA_LAUNCH_CHECK();
   return PA_OK;
 }
@@ -181,18 +187,28 @@ int pa_trajectory_linearize(const pa_traj_args* a, void* stream) {
   return pa_debug_trajectory_linearize(a, 0, nullptr, stream);
 }
 
-int pa_proj_linearize(int n, const double* tbody, const double* pb, const double* z, const double* k, int k_stride,
-                      const double* tcam, int tcam_stride, const double* inv_sigma, double* r, double* j, double* err,
-                      int32_t* status, void* stream) {
+int pa_proj_linearize_robust(int n, const double* tbody, const double* pb, const double* z, const double* k,
+                             int k_stride, const double* tcam, int tcam_stride, const double* inv_sigma,
+                             int robust_kind, double robust_k, double* r, double* j, double* err, int32_t* status,
+                             void* stream) {
+  if (const int rc = pa::robust_check(robust_kind, robust_k, "proj linearize", "robust_kind", "robust_k")) return rc;
   PA_CHECK(n >= 0, "n %d", n);
   if (n == 0) return PA_OK;
   PA_CHECK(tbody && pb && z && k && r, "null pointer");
   PA_CHECK(k_stride == 0 || k_stride == 5, "k_stride must be 0 or 5");
   PA_CHECK(tcam_stride == 0 || tcam_stride == 12, "tcam_stride must be 0 or 12");
-  hipLaunchKernelGGL(pa::proj_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, tbody, pb, z, k,
-                     k_stride, tcam, tcam_stride, inv_sigma, r, j, err, status);
+  const auto kernel = robust_kind == PA_ROBUST_NONE ? pa::proj_kernel<false> : pa::proj_kernel<true>;
+  hipLaunchKernelGGL(kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, tbody, pb, z, k, k_stride, tcam,
+                     tcam_stride, inv_sigma, robust_kind, robust_k, r, j, err, status);
   PA_LAUNCH_CHECK();
   return PA_OK;
+}
+
+int pa_proj_linearize(int n, const double* tbody, const double* pb, const double* z, const double* k, int k_stride,
+                      const double* tcam, int tcam_stride, const double* inv_sigma, double* r, double* j, double* err,
+                      int32_t* status, void* stream) {
+  return pa_proj_linearize_robust(n, tbody, pb, z, k, k_stride, tcam, tcam_stride, inv_sigma, PA_ROBUST_NONE, 0.0, r, j,
+                                  err, status, stream);
 }
 
 }  // extern "C"

@@ -413,12 +413,22 @@ __device__ void cv_one(const double* __restrict__ v1, const double* __restrict__
 // arithmetic (a branch per factor kept the traj kernel's four per-lane factors in
 // sequence, each waiting out its own loads).  Outputs r 2, J 12 (col-major 2x6), err,
 // status.
+// RB: with the noise model's robust part (cam.robust = PA_ROBUST_HUBER / _CAUCHY, cam.rk = k, the
+// same for every factor of a launch; include/perseus_amd.h pa_proj_linearize_robust): sqrt(w)
+// scales r and the two whitening factors of J's rows, err is rho.  RB = false is the plain
+// factor, token for token the code it was before the robust models: the host picks the
+// instantiation, so a launch without a robust model runs what it always ran (bit for bit, at the
+// same registers; a run-time kind in one body moved the compiler's FMA contraction choices in
+// the plain part, 17 of 12288 factors then differed in the last bit).
 struct Cam {
   Pose C;
   double fx, fy, sk, u0, v0, s0, s1;
+  int robust;
+  double rk;
 };
+template <bool RB>
 __device__ __forceinline__ Cam load_cam(const double* __restrict__ K, const double* __restrict__ Tcp,
-                                        const double* __restrict__ isig) {
+                                        const double* __restrict__ isig, int robust, double rk) {
   Cam c;
   if (Tcp) {
     c.C = load_pose(Tcp);
@@ -433,8 +443,36 @@ __device__ __forceinline__ Cam load_cam(const double* __restrict__ K, const doub
   c.v0 = K[4];
   c.s0 = isig ? isig[0] : 1.0;
   c.s1 = isig ? isig[1] : 1.0;
+  c.robust = robust;
+  c.rk = rk;
+  // k in a vector register from here on: as a scalar pair it stays live through the factor and
+  // cost pose_tick_post_kernel a scalar spill (36 B of private segment) and lm_lin_kernel 68 B
+  if constexpr (RB) asm volatile("" : "+v"(c.rk));
   return c;
 }
+// The m-estimator at n = |(r0, r1)|: sw = sqrt(w(n)), rho = rho(n); kind is PA_ROBUST_HUBER or
+// PA_ROBUST_CAUCHY (uniform over the launch; Huber's two sides are a select).  Every operation
+// is rounded on its own (no contraction, the one FMA written out), so the trajectory kernels and
+// proj_kernel give the same bits whatever surrounds the call.  A NaN n (cheirality) gives values
+// the caller overwrites.
+__device__ __forceinline__ void robust_weight(int kind, double k, double r0, double r1, double& sw, double& rho) {
+#pragma clang fp contract(off)
+  const double n2 = __builtin_fma(r0, r0, r1 * r1);
+  if (kind == PA_ROBUST_HUBER) {
+    const double n = sqrt(n2);
+    const bool out = n > k;
+    const double hk = 0.5 * k;
+    sw = out ? sqrt(k / n) : 1.0;
+    rho = out ? k * (n - hk) : 0.5 * n2;
+  } else {
+    const double k2 = k * k, q = n2 / k2;
+    const double hk2 = 0.5 * k2;
+    sw = sqrt(1.0 / (1.0 + q));
+    rho = hk2 * log1p(q);
+  }
+}
+
+template <bool RB>
 __device__ __forceinline__ void proj_eval(const Pose& T, V3 pb, double zx, double zy, const Cam& cam, double (&r_out)[2],
                                           double (&J)[12], double& err, int32_t& status) {
   const Pose& C = cam.C;
@@ -448,6 +486,9 @@ __device__ __forceinline__ void proj_eval(const Pose& T, V3 pb, double zx, doubl
   const double x = pc.x * iz, y = pc.y * iz;
   const double u = fx * x + sk * y + u0, v = fy * y + v0;
   const double r0 = (u - zx) * s0, r1 = (v - zy) * s1;
+  double sw = 1.0, rho = 0.0;
+  if constexpr (RB) robust_weight(cam.robust, cam.rk, r0, r1, sw, rho);
+  const double s0w = RB ? s0 * sw : s0, s1w = RB ? s1 * sw : s1;
   // dproj_dpoint = Dcal * Dpn * Rc^T (2x3), Dcal = [[fx, s],[0, fy]], Dpn = 1/z [[1,0,-x],[0,1,-y]]
   double Dpn[2][3] = {{iz, 0.0, -x * iz}, {0.0, iz, -y * iz}};
   double Dp[2][3];
@@ -468,25 +509,33 @@ __device__ __forceinline__ void proj_eval(const Pose& T, V3 pb, double zx, doubl
       for (int k = 0; k < 3; ++k) sacc += Dw[rr][k] * (c < 3 ? RS(k, c) : T.R(k, c - 3));
       h[rr] = sacc;
     }
-    J[c * 2] = ok ? h[0] * s0 : nan;  // H0 = dproj_dpoint @ dpc_dpose (:264), column-major
-    J[c * 2 + 1] = ok ? h[1] * s1 : nan;
+    J[c * 2] = ok ? h[0] * s0w : nan;  // H0 = dproj_dpoint @ dpc_dpose (:264), column-major
+    J[c * 2 + 1] = ok ? h[1] * s1w : nan;
   }
-  r_out[0] = ok ? r0 : nan;
-  r_out[1] = ok ? r1 : nan;
-  err = ok ? 0.5 * (r0 * r0 + r1 * r1) : nan;
+  if constexpr (RB) {
+    r_out[0] = ok ? r0 * sw : nan;
+    r_out[1] = ok ? r1 * sw : nan;
+    err = ok ? rho : nan;
+  } else {
+    r_out[0] = ok ? r0 : nan;
+    r_out[1] = ok ? r1 : nan;
+    err = ok ? 0.5 * (r0 * r0 + r1 * r1) : nan;
+  }
   status = ok ? 0 : 1;
 }
 
 // One KeypointProjectionFactor.  K: 5 values; Tc: 12 values or null (identity);
 // outputs r 2, J 12 (col-major 2x6) or null, err / status or null.
+template <bool RB>
 __device__ void proj_one(const double* __restrict__ Tb, V3 pb, double zx, double zy, const double* __restrict__ K,
-                         const double* __restrict__ Tcp, const double* __restrict__ isig, double* __restrict__ r_out,
-                         double* __restrict__ J, double* __restrict__ err, int32_t* __restrict__ status) {
+                         const double* __restrict__ Tcp, const double* __restrict__ isig, int robust, double rk,
+                         double* __restrict__ r_out, double* __restrict__ J, double* __restrict__ err,
+                         int32_t* __restrict__ status) {
   const Pose T = load_pose(Tb);
-  const Cam cam = load_cam(K, Tcp, isig);
+  const Cam cam = load_cam<RB>(K, Tcp, isig, robust, rk);
   double r[2], Jl[12], e;
   int32_t st;
-  proj_eval(T, pb, zx, zy, cam, r, Jl, e, st);
+  proj_eval<RB>(T, pb, zx, zy, cam, r, Jl, e, st);
   r_out[0] = r[0];
   r_out[1] = r[1];
   if (err) *err = e;
@@ -724,6 +773,8 @@ __device__ __forceinline__ void traj_dyn_block(const pa_traj_args& a, long blk, 
 namespace trj {
 constexpr int PPW = 4;  // projection factors per lane
 }
+// (RB: a.robust_proj names a robust model, proj_eval<true>)
+template <bool RB>
 __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, double* st, unsigned long long* ts) {
   using trj::PPW;
   const int lane = threadIdx.x & 63;
@@ -737,7 +788,7 @@ __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, do
     int n[PPW];
     // every operand of the PPW factors is loaded before any is used (proj_eval is
     // branch-free, so the loads of all PPW chains are in flight together)
-    const Cam cam = load_cam(a.K, a.tcam, a.isig_proj);
+    const Cam cam = load_cam<RB>(a.K, a.tcam, a.isig_proj, a.robust_proj, a.robust_proj_k);
     Pose T[PPW];
     V3 pb[PPW];
     float2 yv[PPW];
@@ -760,7 +811,7 @@ __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, do
     for (int h = 0; h < PPW; ++h) {
       const float px = kornia_denorm(yv[h].x, a.W);
       const float py = kornia_denorm(yv[h].y, a.H);
-      proj_eval(T[h], pb[h], (double)px, (double)py, cam, r[h], J[h], e[h], stt[h]);
+      proj_eval<RB>(T[h], pb[h], (double)px, (double)py, cam, r[h], J[h], e[h], stt[h]);
       if (off[h]) {  // no measurement yet: status 2, zero residual / Jacobian / error
         r[h][0] = r[h][1] = 0.0;
 #pragma unroll
@@ -827,13 +878,14 @@ __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, do
 constexpr int TICK_LIN_W = 6;
 constexpr int LIN_STAGE = trj::STAGE + 4 * trj::UNIT;
 static_assert(LIN_STAGE * 8 <= 96 * 1024, "factor staging");
+template <bool RB>
 __device__ __forceinline__ void traj_lin_block(const pa_traj_args& a1, double* st) {
   const int wv = threadIdx.x >> 6;
   const int wp = (a1.L * a1.n_kp + 64 * trj::PPW - 1) / (64 * trj::PPW);  // projection units (<= 2); unit wp: constant velocity
   if (wv < 2) {
     traj_dyn_block(a1, 0, st, nullptr);  // (its one LDS barrier is matched by every other wave's below)
   } else {
-    if (wv - 2 <= wp) traj_unit_wave(a1, wv - 2, st + trj::STAGE + (wv - 2) * trj::UNIT, nullptr);
+    if (wv - 2 <= wp) traj_unit_wave<RB>(a1, wv - 2, st + trj::STAGE + (wv - 2) * trj::UNIT, nullptr);
     lds_barrier();
   }
 }

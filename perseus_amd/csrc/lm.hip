@@ -54,7 +54,9 @@ __device__ __forceinline__ void lm_copy(V* dst, const V* src, long n) {
 }
 
 // launch k = 0: the initial state (ta.pose / vel / angvel) into set 0; k >= 1: the trial state of
-// iteration k into the set that is not current, then the decision
+// iteration k into the set that is not current, then the decision.  RB: ta.robust_proj names a
+// robust noise model (the cost is then the sum of its rho; the decision logic is the same)
+template <bool RB>
 __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta, LmDev d, int k) {
   __shared__ __attribute__((aligned(16))) double st[LIN_STAGE];
   __shared__ int dec_s;
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta
     a1.pose = k > 0 ? d.pose + f0 * 12 : xp;  // (the trial state)
     a1.vel = k > 0 ? d.vel + f0 * 3 : xv;
     a1.angvel = k > 0 ? d.angvel + f0 * 3 : xw;
-    traj_lin_block(a1, st);
+    traj_lin_block<RB>(a1, st);
   }
   if (k == 0)
     for (int e = 1 + (int)threadIdx.x; e < M1; e += 64 * TICK_LIN_W) d.hist[(size_t)t * M1 + e] = NAN;
@@ -238,6 +240,7 @@ static int lm_solve_impl(const pa_traj_args* ta, const pa_lm_params* p, int pend
                          int32_t* iters, int32_t* status, double* lambda, double* cost_hist, void* ws,
                          size_t ws_bytes, void* stream) {
   PA_CHECK(ta && p, "lm: null args / params");
+  if (const int rc = pa::robust_check(*ta, "lm")) return rc;
   const int T = ta->T, L = ta->L, K = ta->n_kp;
   PA_CHECK(T >= 0 && L >= 2 && L <= pa::GN_CR_LMAX && K >= 1 && K <= pa::GN_KMAX,
            "lm: T %d, L %d (2..%d), n_kp %d (1..%d)", T, L, pa::GN_CR_LMAX, K, pa::GN_KMAX);
@@ -286,13 +289,14 @@ static int lm_solve_impl(const pa_traj_args* ta, const pa_lm_params* p, int pend
   d.p = *p;
   d.pending = pending;
   const hipStream_t s = (hipStream_t)stream;
+  const auto lin_kernel = ta->robust_proj == PA_ROBUST_NONE ? pa::lm_lin_kernel<false> : pa::lm_lin_kernel<true>;
   for (int k = 0; k <= p->max_iters; ++k) {
     if (k > 0)
       pa::gn_for_kp(K, [&](auto rp) {
         hipLaunchKernelGGL(pa::lm_step_kernel<decltype(rp)::value>, dim3(T), dim3(64 * pa::GN_CR_W), 0, s, T, L, K, d,
                            ta->pose, ta->vel, ta->angvel);
       });
-    hipLaunchKernelGGL(pa::lm_lin_kernel, dim3(T), dim3(64 * pa::TICK_LIN_W), 0, s, *ta, d, k);
+    hipLaunchKernelGGL(lin_kernel, dim3(T), dim3(64 * pa::TICK_LIN_W), 0, s, *ta, d, k);
   }
   PA_LAUNCH_CHECK();
   return PA_OK;

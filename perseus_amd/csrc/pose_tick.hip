@@ -22,6 +22,9 @@ namespace pa {
 // frame L - 1's projection factors (evaluated on the stale keypoints the slot still holds)
 // are marked status 3 afterwards, so the GN assembly gives them zero rows; the post half
 // evaluates them on y_new.
+// RB (here and in pose_tick_post_kernel): ta.robust_proj names a robust noise model for the
+// projection factors (proj_eval<true>); the host picks the instantiation.
+template <bool RB>
 __global__ __launch_bounds__(64 * TICK_LIN_W) void pose_tick_lin_kernel(pa_traj_args ta, const float* __restrict__ y_new) {
   __shared__ __attribute__((aligned(16))) double st[LIN_STAGE];
   const int t = blockIdx.x, L = ta.L, K = ta.n_kp;
@@ -30,7 +33,7 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void pose_tick_lin_kernel(pa_traj_
                       ta.vel_frame, const_cast<int32_t*>(ta.nvalid));
   __syncthreads();
   const pa_traj_args a1 = traj_view(ta, t, factor_set(ta));
-  traj_lin_block(a1, st);
+  traj_lin_block<RB>(a1, st);
   if (!y_new) {  // (uniform)
     __syncthreads();  // the unit waves' status stores come first
     if ((int)threadIdx.x < K) a1.status[(long)(L - 1) * K + threadIdx.x] = 3;
@@ -72,6 +75,7 @@ __global__ __launch_bounds__(64 * GN_CR_W, 1) void pose_tick_pre_kernel(GnArgs g
   gn_cr_run<RP, NS, true>(g, blockIdx.x, fb, pool);
 }
 
+template <bool RB>
 __global__ __launch_bounds__(64 * GN_CR_W, 1) void pose_tick_post_kernel(pa_traj_args ta, const float* __restrict__ y_new,
                                                                           const double* __restrict__ ws, double* delta,
                                                                           int32_t* info, double* newest) {
@@ -108,7 +112,7 @@ __global__ __launch_bounds__(64 * GN_CR_W, 1) void pose_tick_post_kernel(pa_traj
     // lane k, traj_unit_wave's evaluation
     if (i < ny) const_cast<float*>(ta.y)[fn * ny + i] = y_new[(size_t)t * ny + i];
     if (i < K) {
-      const Cam cam = load_cam(ta.K, ta.tcam, ta.isig_proj);
+      const Cam cam = load_cam<RB>(ta.K, ta.tcam, ta.isig_proj, ta.robust_proj, ta.robust_proj_k);
       const Pose T = load_pose(ta.pose + fn * 12);
       const V3 pb = load3(ta.corners + 3 * i);
       const float px = kornia_denorm(y_new[(size_t)t * ny + 2 * i], ta.W);
@@ -116,7 +120,7 @@ __global__ __launch_bounds__(64 * GN_CR_W, 1) void pose_tick_post_kernel(pa_traj
       const bool off = ta.nvalid ? L - 1 < L - ta.nvalid[t] : false;
       double r[2], J[12], e;
       int32_t st;
-      proj_eval(T, pb, (double)px, (double)py, cam, r, J, e, st);
+      proj_eval<RB>(T, pb, (double)px, (double)py, cam, r, J, e, st);
       if (off) {
         r[0] = r[1] = 0.0;
 #pragma unroll
@@ -206,6 +210,7 @@ size_t pa_window_pose_tick_workspace(int T, int L) {
 // returns) before the pointers are looked at
 static int pose_tick_check(const pa_traj_args* ta, double lambda, const char* who) {
   PA_CHECK(ta, "%s: null args", who);
+  if (const int rc = pa::robust_check(*ta, who)) return rc;
   const int T = ta->T, L = ta->L, K = ta->n_kp;
   // one workgroup per trajectory: correct at any T (the CU count is a performance choice of the
   // caller, StreamingPipeline's fused_pose / split_pose eligibility)
@@ -227,6 +232,12 @@ static int pose_tick_ws_check(const pa_traj_args* ta, const void* ws, size_t ws_
   return PA_OK;
 }
 
+// advance + linearize (y_new null: the split tick's pre half), with or without a robust noise model
+static void launch_lin(const pa_traj_args* ta, const float* y_new, hipStream_t s) {
+  const auto kernel = ta->robust_proj == PA_ROBUST_NONE ? pa::pose_tick_lin_kernel<false> : pa::pose_tick_lin_kernel<true>;
+  hipLaunchKernelGGL(kernel, dim3(ta->T), dim3(64 * pa::TICK_LIN_W), 0, s, *ta, y_new);
+}
+
 // the cyclic reduction in the ROOT order into the tick workspace (the pre half's second launch)
 static void launch_pre(const pa_traj_args* ta, double lambda, void* ws, hipStream_t s) {
   const pa::GnArgs g = pa::gn_args(*ta, lambda, nullptr, nullptr, (double*)ws);
@@ -243,7 +254,7 @@ int pa_window_pose_tick(const pa_traj_args* ta, const float* y_new, double lambd
   const int T = ta->T;
   const pa::GnArgs g = pa::gn_args(*ta, lambda, delta, info, nullptr);
   const hipStream_t s = (hipStream_t)stream;
-  if (!(pa::g_gn_na & 2048)) hipLaunchKernelGGL(pa::pose_tick_lin_kernel, dim3(T), dim3(64 * pa::TICK_LIN_W), 0, s, *ta, y_new);
+  if (!(pa::g_gn_na & 2048)) launch_lin(ta, y_new, s);
   if (pa::g_gn_na & 1024) { PA_LAUNCH_CHECK(); return PA_OK; }
   double* pose = const_cast<double*>(ta->pose);
   double* angvel = const_cast<double*>(ta->angvel);
@@ -261,7 +272,7 @@ int pa_window_pose_tick_pre(const pa_traj_args* ta, double lambda, void* ws, siz
   if (rc != PA_OK || ta->T == 0) return rc;
   if ((rc = pose_tick_ws_check(ta, ws, ws_bytes, "pose tick pre")) != PA_OK) return rc;
   const hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(pa::pose_tick_lin_kernel, dim3(ta->T), dim3(64 * pa::TICK_LIN_W), 0, s, *ta, nullptr);
+  launch_lin(ta, nullptr, s);
   launch_pre(ta, lambda, ws, s);
   PA_LAUNCH_CHECK();
   return PA_OK;
@@ -282,8 +293,9 @@ int pa_window_pose_tick_post(const pa_traj_args* ta, const float* y_new, const v
   if (rc != PA_OK || ta->T == 0) return rc;
   PA_CHECK(y_new && delta && info, "pose tick post: null y_new / delta / info");
   if ((rc = pose_tick_ws_check(ta, ws, ws_bytes, "pose tick post")) != PA_OK) return rc;
-  hipLaunchKernelGGL(pa::pose_tick_post_kernel, dim3(ta->T), dim3(64 * pa::GN_CR_W), 0, (hipStream_t)stream, *ta, y_new,
-                     (const double*)ws, delta, info, newest_pose);
+  const auto kernel = ta->robust_proj == PA_ROBUST_NONE ? pa::pose_tick_post_kernel<false> : pa::pose_tick_post_kernel<true>;
+  hipLaunchKernelGGL(kernel, dim3(ta->T), dim3(64 * pa::GN_CR_W), 0, (hipStream_t)stream, *ta, y_new, (const double*)ws,
+                     delta, info, newest_pose);
   PA_LAUNCH_CHECK();
   return PA_OK;
 }

@@ -53,13 +53,17 @@ def _isig(sigmas, dim, dev):
 def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: int, dt: float,
                          vel_frame: str = "world", camera_pose=None, H: int = 256, W: int = 256,
                          proj_sigmas=None, dyn_sigmas=None, cv_sigmas=None, jacobians: bool = True,
-                         nvalid: torch.Tensor | None = None):
+                         nvalid: torch.Tensor | None = None, proj_robust=None):
     """Stage inputs on the device and allocate outputs: returns (args, out).  `args`
     (a pa_traj_args) can be launched repeatedly with `launch(args, device)`; `out`
     holds the output tensors (Jacobians as (n, cols, rows) column-major buffers) and
     keeps every staged input alive.  nvalid (optional, int32 (T,) on the device, read at
     every launch): frames with a measurement, counted from the window's end; the projection
-    factors of the others get status 2 and zero residual / Jacobian (the GN step skips them)."""
+    factors of the others get status 2 and zero residual / Jacobian (the GN step skips them).
+    proj_robust: None, ("huber", k) or ("cauchy", k), k in whitened units: GTSAM's
+    noiseModel.Robust on the projection factors (r_proj and j_proj sqrt(w)-scaled, err_proj the
+    m-estimator's loss; pa_traj_args.robust_proj); every consumer of the outputs (gn_step,
+    marginals, lm_solve, the streaming ticks) then does IRLS unchanged."""
     if y.device.type != "cuda":
         raise RuntimeError("linearize_trajectories expects the detector output on the GPU (no CPU fallback)")
     if vel_frame not in ("world", "body"):
@@ -82,7 +86,7 @@ def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T
     def e(*shape, dtype=torch.float64):
         return torch.empty(shape, dtype=dtype, device=dev)
 
-    out = {"r_proj": e(n, 2), "status": e(n, dtype=torch.int32), "err_proj": e(n) if isp is not None else None,
+    out = {"r_proj": e(n, 2), "status": e(n, dtype=torch.int32), "err_proj": e(n) if isp is not None or proj_robust is not None else None,
            "r_dyn": e(m, 6), "err_dyn": e(m) if isd is not None else None,
            "r_cv": e(m, 3), "err_cv": e(m) if isc is not None else None}
     for k, shp in _JAC.items():
@@ -99,6 +103,7 @@ def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T
                                or not nvalid.is_contiguous()):
         raise RuntimeError(f"nvalid must be a contiguous int32 ({T},) tensor on {dev}")
     a.nvalid = _lib.ptr(nvalid)
+    a.robust_proj, a.robust_proj_k = _lib.robust_code(proj_robust)
     for k in ("r_proj", "err_proj", "status", "r_dyn", "err_dyn", "r_cv", "err_cv", *_JAC):
         setattr(a, k, _lib.ptr(out[k]))
     out["_keep"] = (y, P, V, Wv, Cn, Kt, Tc, isp, isd, isc, nvalid)  # inputs stay alive until the stream drains
@@ -312,7 +317,7 @@ class LMPlan:
 def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: int, dt: float, proj_sigmas, dyn_sigmas,
              cv_sigmas, nvalid: torch.Tensor | None = None, vel_frame: str = "world", camera_pose=None, H: int = 256,
              W: int = 256, newest_pending: bool = False, covariance: bool = False, cov_lambda: float = 1e-9,
-             **params) -> dict:
+             proj_robust=None, **params) -> dict:
     """Smoothed trajectories: Levenberg-Marquardt over all factors of T trajectories x L frames
     from the keypoints `y` (device) and the initial state, on the device (pa_trajectory_lm_solve;
     layouts as linearize_trajectories, the inputs are not modified).  Returns pose (T*L, 12),
@@ -322,12 +327,14 @@ def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: in
     max_iters, lambda0, lambda_up, lambda_down, lambda_min, lambda_max, rel_tol, abs_tol.
     covariance=True: also cov (T*L, 12, 12) and cov_info (T,), the marginal covariances
     (pipeline.marginals) of the linearization the solve leaves at the final state, with
-    lam = cov_lambda (partly filled or pending windows need about 1e-2, see MarginalsPlan)."""
+    lam = cov_lambda (partly filled or pending windows need about 1e-2, see MarginalsPlan).
+    proj_robust: as prepare_trajectories; the cost is then the sum of the m-estimator's losses and
+    the covariance that of the sqrt(w)-weighted system at the final state."""
     dev = y.device
     P, V, Wv = (_f64(a, dev).clone() for a in (poses, vels, angvels))  # updated in place: never the caller's
     a, lin = prepare_trajectories(y, P, V, Wv, corners, K, T=T, L=L, dt=dt, vel_frame=vel_frame,
                                   camera_pose=camera_pose, H=H, W=W, proj_sigmas=proj_sigmas, dyn_sigmas=dyn_sigmas,
-                                  cv_sigmas=cv_sigmas, nvalid=nvalid)
+                                  cv_sigmas=cv_sigmas, nvalid=nvalid, proj_robust=proj_robust)
     P, V, Wv = lin["_keep"][1:4]
     plan = LMPlan(a, lin, T=T, L=L, newest_pending=newest_pending, **params)
     plan.launch()

@@ -9,7 +9,10 @@ Reference surface mirrored (GTSAM CustomFactor callbacks, `factors.py:8-275`):
   each with `keys()`, `error_func(this, v, H=None)` (H entries overwritten with f64
   arrays of shape (dim r, dim key), exactly like the reference), `unwhitenedError(v)`,
   `error(v)` = 0.5 ||r / sigma||^2 and `linearize(v)` -> ([A_i], b) with
-  A_i = H_i / sigma, b = -r / sigma (GTSAM NoiseModelFactor semantics).
+  A_i = H_i / sigma, b = -r / sigma (GTSAM NoiseModelFactor semantics).  With
+  `noiseModel.Robust.Create(noiseModel.mEstimator.Huber.Create(k), base)` (or `.Cauchy`)
+  `error(v)` is the m-estimator's loss at |r / sigma| and `linearize(v)` scales A_i and b by
+  sqrt(weight), as GTSAM's Robust::WhitenSystem does.
 
 All arithmetic runs in the f64 HIP kernels of libperseus_amd.so; a single-factor call
 is a batch of one (correct, not fast); use `linearize_*` for batches.  `Values`,
@@ -97,9 +100,81 @@ class _Isotropic(_Diagonal):
         return cls(np.full(dim, float(sigma)))
 
 
+class _MEstimator:
+    """gtsam.noiseModel.mEstimator.Base subset: weight(n) and loss(n) at the whitened
+    residual norm n = |r / sigma|_2, with k in whitened units (include/perseus_amd.h)."""
+
+    kind = ""
+
+    def __init__(self, k):
+        k = float(k)
+        if not (np.isfinite(k) and k > 0.0):
+            raise ValueError(f"mEstimator.{type(self).__name__}: k must be a positive finite number, got {k}")
+        self.k = k
+
+    @classmethod
+    def Create(cls, k):
+        return cls(k)
+
+    def sqrtWeight(self, n) -> float:
+        return float(np.sqrt(self.weight(n)))
+
+
+class _Huber(_MEstimator):
+    kind = "huber"
+
+    def weight(self, n) -> float:
+        n = abs(float(n))
+        return 1.0 if n <= self.k else self.k / n
+
+    def loss(self, n) -> float:
+        n = abs(float(n))
+        return 0.5 * n * n if n <= self.k else self.k * (n - 0.5 * self.k)
+
+
+class _Cauchy(_MEstimator):
+    kind = "cauchy"
+
+    def weight(self, n) -> float:
+        return 1.0 / (1.0 + float(n) ** 2 / self.k ** 2)
+
+    def loss(self, n) -> float:
+        return 0.5 * self.k ** 2 * float(np.log1p(float(n) ** 2 / self.k ** 2))
+
+
+class _mEstimator:  # noqa: N801  (gtsam.noiseModel.mEstimator namespace)
+    Huber = _Huber
+    Cauchy = _Cauchy
+
+
+class _Robust:
+    """gtsam.noiseModel.Robust: an m-estimator over a Diagonal / Isotropic base.  error = rho(n),
+    the linearized rows are sqrt(w(n)) times the base's whitened ones (Robust::WhitenSystem)."""
+
+    def __init__(self, robust, noise):
+        if not (hasattr(robust, "weight") and hasattr(robust, "loss")):
+            raise TypeError("noiseModel.Robust.Create(mEstimator, base noise model)")
+        self._robust, self._noise = robust, noise
+
+    @classmethod
+    def Create(cls, robust, noise):
+        return cls(robust, noise)
+
+    def robust(self):
+        return self._robust
+
+    def noise(self):
+        return self._noise
+
+    def sigmas(self):
+        return self._noise.sigmas()
+
+
 class noiseModel:  # noqa: N801  (gtsam.noiseModel namespace)
     Diagonal = _Diagonal
     Isotropic = _Isotropic
+    mEstimator = _mEstimator
+    Robust = _Robust
 
 
 class Values:
@@ -200,10 +275,12 @@ def linearize_const_vel(v1, v2, inv_sigma=None):
     return {"r": r, "J0": J0.transpose(1, 2), "J1": J1.transpose(1, 2), "err": err}
 
 
-def linearize_projection(Tbody, p_b, z, K, Tcam=None, inv_sigma=None, jacobians=True):
+def linearize_projection(Tbody, p_b, z, K, Tcam=None, inv_sigma=None, jacobians=True, robust=None):
     """Batched KeypointProjectionFactor (factors.py:216-275).  K: (5,) shared or (n,5);
     Tcam: None (identity), (12,) shared or (n,12).  Returns r (n,2), J (n,2,6), status (n,)
-    (1 = cheirality), err (n,) if inv_sigma."""
+    (1 = cheirality), err (n,) if inv_sigma.  robust: None, ("huber", k) or ("cauchy", k)
+    (pa_proj_linearize_robust): r and J are then sqrt(w)-scaled and err is the m-estimator's
+    loss at |r / sigma| (err is returned with unit sigma too)."""
     dev = _device()
     Tb, pb, zz = _dev(Tbody, dev), _dev(p_b, dev), _dev(z, dev)
     n = Tb.shape[0]
@@ -215,10 +292,17 @@ def linearize_projection(Tbody, p_b, z, K, Tcam=None, inv_sigma=None, jacobians=
     r = torch.empty((n, 2), dtype=torch.float64, device=dev)
     J = torch.empty((n, 6, 2), dtype=torch.float64, device=dev) if jacobians else None
     st = torch.empty(n, dtype=torch.int32, device=dev)
-    err = torch.empty(n, dtype=torch.float64, device=dev) if isg is not None else None
-    _lib.check(_lib.lib().pa_proj_linearize(n, Tb.data_ptr(), pb.data_ptr(), zz.data_ptr(), Kt.data_ptr(), ks,
-                                            _lib.ptr(Tc), ts, _lib.ptr(isg), r.data_ptr(), _lib.ptr(J),
-                                            _lib.ptr(err), st.data_ptr(), _lib.stream_of(dev)), "pa_proj_linearize")
+    kind, rk = _lib.robust_code(robust)
+    err = torch.empty(n, dtype=torch.float64, device=dev) if isg is not None or kind else None
+    if kind:
+        _lib.check(_lib.lib().pa_proj_linearize_robust(
+            n, Tb.data_ptr(), pb.data_ptr(), zz.data_ptr(), Kt.data_ptr(), ks, _lib.ptr(Tc), ts, _lib.ptr(isg), kind,
+            rk, r.data_ptr(), _lib.ptr(J), _lib.ptr(err), st.data_ptr(), _lib.stream_of(dev)),
+            "pa_proj_linearize_robust")
+    else:
+        _lib.check(_lib.lib().pa_proj_linearize(n, Tb.data_ptr(), pb.data_ptr(), zz.data_ptr(), Kt.data_ptr(), ks,
+                                                _lib.ptr(Tc), ts, _lib.ptr(isg), r.data_ptr(), _lib.ptr(J),
+                                                _lib.ptr(err), st.data_ptr(), _lib.stream_of(dev)), "pa_proj_linearize")
     out = {"r": r, "status": st, "err": err}
     if jacobians:
         out["J"] = J.transpose(1, 2)
@@ -245,17 +329,36 @@ class _Factor:
     def unwhitenedError(self, v, H=None):
         return self.error_func(self, v, H)
 
+    def _sigmas(self, r):
+        nm = self._noise
+        if nm is None:
+            return np.ones_like(r)
+        return nm.sigmas() if hasattr(nm, "sigmas") else nm.noise().sigmas()  # (gtsam's Robust has no sigmas())
+
+    def _m_estimator(self):
+        """The noise model's m-estimator (noiseModel.Robust) or None."""
+        rob = getattr(self._noise, "robust", None)
+        return rob() if callable(rob) else None
+
     def error(self, v) -> float:
+        """0.5 |r / sigma|^2, or with a noiseModel.Robust the m-estimator's loss at |r / sigma|."""
         r = self.error_func(self, v)
-        s = self._noise.sigmas() if self._noise is not None else np.ones_like(r)
-        rw = r / s
+        rw = r / self._sigmas(r)
+        m = self._m_estimator()
+        if m is not None:
+            return float(m.loss(float(np.sqrt(rw @ rw))))
         return 0.5 * float(rw @ rw)
 
     def linearize(self, v):
         H = [None] * len(self._keys)
         r = self.error_func(self, v, H)
-        s = self._noise.sigmas() if self._noise is not None else np.ones_like(r)
-        return [h / s[:, None] for h in H], -r / s
+        s = self._sigmas(r)
+        A, b = [h / s[:, None] for h in H], -r / s
+        m = self._m_estimator()
+        if m is not None:  # Robust::WhitenSystem: sqrt(w) on every row
+            sw = float(np.sqrt(m.weight(float(np.sqrt(b @ b)))))
+            A, b = [sw * a for a in A], sw * b
+        return A, b
 
 
 class PoseDynamicsFactor(_Factor):

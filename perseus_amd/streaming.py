@@ -56,7 +56,10 @@ class StreamingPipeline:
     datagen camera and cube, synth.CAMERA_K / CUBE_CORNERS); dt = the camera period;
     sigmas of the diagonal noise models (pixels, dynamics tangent, velocity); lam = the
     LM damping; init_pose (n_cams, 12) / init_vel / init_angvel fill every frame of the
-    initial window (default: the cube 0.4 m in front of each camera, at rest)."""
+    initial window (default: the cube 0.4 m in front of each camera, at rest);
+    proj_robust = None, ("huber", k) or ("cauchy", k): GTSAM's noiseModel.Robust on the keypoint
+    factors (pipeline.prepare_trajectories), so that a keypoint tens of pixels off, an occluded
+    corner, is down-weighted in every tick form, solve_window() and window_covariance()."""
 
     def __init__(self, model, n_cams: int = 3, src_hw=(720, 1280), bgr: bool = True, host_crop: bool = True,
                  graph: bool = True, near: float | None = None, far: float | None = None, device=None,
@@ -64,7 +67,7 @@ class StreamingPipeline:
                  proj_sigma: float = 1.0, dyn_sigma: float = 0.1, cv_sigma: float = 0.1, lam: float = 1e-2,
                  init_pose=None, init_vel=None, init_angvel=None, split_k: bool = True,
                  zero_copy: bool | None = None, split_pose: bool = True, pre_ahead: bool = False,
-                 zero_copy_out: bool = True):
+                 zero_copy_out: bool = True, proj_robust=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingPipeline needs a ROCm GPU (no CPU fallback)")
         cam_K = K  # (the name K is the keypoint count below)
@@ -161,7 +164,7 @@ class StreamingPipeline:
         self.fused_pose = self.split_pose = self.pre_ahead = False
         if self.pose_L:
             self._init_pose_stage(cam_K, corners, dt, vel_frame, proj_sigma, dyn_sigma, cv_sigma, lam, init_pose,
-                                  init_vel, init_angvel)
+                                  init_vel, init_angvel, proj_robust)
         self.graph = None
         self.pre_graph = None
         with torch.cuda.stream(self.stream):
@@ -256,7 +259,7 @@ class StreamingPipeline:
         pipeline.window_retract(self.win, self.gn.out["delta"], self.gn.out["info"], newest=self.pose_d)
 
     def _init_pose_stage(self, K, corners, dt, vel_frame, proj_sigma, dyn_sigma, cv_sigma, lam, init_pose, init_vel,
-                         init_angvel):
+                         init_angvel, proj_robust=None):
         n, Lw, nk, dev = self.n, self.pose_L, self.model.n_keypoints, self.dev
         if Lw < 2:
             raise ValueError("pose_window must be >= 2 frames (the dynamics factors couple frame pairs)")
@@ -282,7 +285,7 @@ class StreamingPipeline:
             self.win["y"].view(n * Lw, 2 * nk), self.win["pose"].view(n * Lw, 12), self.win["vel"].view(n * Lw, 3),
             self.win["angvel"].view(n * Lw, 3), corners, K, T=n, L=Lw, dt=self.dt, vel_frame=vel_frame, H=self.H,
             W=self.W, proj_sigmas=[proj_sigma] * 2, dyn_sigmas=[dyn_sigma] * 6, cv_sigmas=[cv_sigma] * 3,
-            nvalid=self.nvalid)
+            nvalid=self.nvalid, proj_robust=proj_robust)
         for k in ("y", "pose", "vel", "angvel"):  # linearize reads the window in place, no staging copy
             assert self.lin["_keep"][("y", "pose", "vel", "angvel").index(k)].data_ptr() == self.win[k].data_ptr()
         self.gn = pipeline.GNPlan(self.lin, T=n, L=Lw, lam=lam)
