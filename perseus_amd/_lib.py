@@ -43,6 +43,21 @@ class LMParams(C.Structure):
                 ("rel_tol", C.c_double), ("abs_tol", C.c_double)]
 
 
+class DebugTap(C.Structure):
+    """Mirror of `pa_debug_tap` (include/perseus_amd_debug.h)."""
+
+    _fields_ = [("in_", C.c_void_p), ("res", C.c_void_p), ("out", C.c_void_p), ("out2", C.c_void_p),
+                ("cap", C.c_size_t), ("in_bytes", C.c_size_t), ("res_bytes", C.c_size_t),
+                ("out_bytes", C.c_size_t), ("out2_bytes", C.c_size_t), ("name", C.c_char_p),
+                ("conv", C.c_int), ("conv2", C.c_int), ("flags", C.c_int), ("B", C.c_int), ("Hin", C.c_int),
+                ("Cin", C.c_int), ("Hout", C.c_int), ("Cout", C.c_int), ("ks", C.c_int), ("stride", C.c_int)]
+
+
+TAP_RELU = 1
+TAP_RES = 2
+TAP_MAXPOOL = 4
+TAP_HEAD = 8
+
 LM_CONVERGED = 1
 LM_MAX_ITERS = 2
 LM_STALLED = 3
@@ -73,6 +88,8 @@ _SIGS = {
                                           C.c_int, C.c_void_p, C.c_void_p]),
     "pa_detector_debug_set_variant": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pa_detector_debug_set_trace": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pa_detector_debug_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.POINTER(DebugTap)]),
     "pa_debug_timing_variants_built": (C.c_int, []),
     "pa_preprocess_rgbd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -214,6 +214,11 @@ __global__ __launch_bounds__(WM* WN * 64 * KSP) void conv3x3_patch(ConvArgs a, i
   }
 
   f32x4 acc[TM][TN];
+  // f32: each channel block's 9 x 32 products are summed on their own and the block sums added up
+  // (tot), so an output's rounding error grows with the block, not with the whole K: one chain of
+  // K / 4 dependent f32 MFMAs is a sequential fmaf sum (single-launch checks)
+  constexpr bool BLOCKED = std::is_same<T, float>::value;
+  f32x4 tot[BLOCKED ? TM : 1][BLOCKED ? TN : 1];
   Tile cur = decode(blockIdx.x);
   const int my_tiles = blockIdx.x + (TPW - 1) * (int)gridDim.x < ntiles
                            ? TPW
@@ -239,7 +244,10 @@ __global__ __launch_bounds__(WM* WN * 64 * KSP) void conv3x3_patch(ConvArgs a, i
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < TN; ++j) {
+        acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (BLOCKED) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
 
     // One K-step (cb, ST): refill register set ST%3 with W(s+3), MFMAs on the
     // staged W(s) and patch(cb), then W(s+1) (set (ST+1)%3) -> the other LDS
@@ -307,6 +315,15 @@ __global__ __launch_bounds__(WM* WN * 64 * KSP) void conv3x3_patch(ConvArgs a, i
       step(cb, ic<6>{});
       step(cb, ic<7>{});
       step(cb, ic<8>{});
+      if constexpr (BLOCKED) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            tot[i][j] += acc[i][j];
+            acc[i][j] = cb + 1 < NCB ? f32x4{0.f, 0.f, 0.f, 0.f} : tot[i][j];
+          }
+      }
     }
 
     if constexpr (KSP == 2) {

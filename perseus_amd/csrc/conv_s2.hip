@@ -185,12 +185,17 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
   }
 
   f32x4 acc[TM][TN], accd[TM][TN];
+  // f32: the conv's products are summed per channel block and the block sums added up (tot), as
+  // conv_patch.hip does: one chain of K / 4 dependent f32 MFMAs is a sequential fmaf sum
+  constexpr bool BLOCKED = std::is_same<T, float>::value;
+  f32x4 tot[BLOCKED ? TM : 1][BLOCKED ? TN : 1];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
       accd[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (BLOCKED) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 
   load_patch(0);
@@ -257,6 +262,15 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
     step(cb, sc<6>{});
     step(cb, sc<7>{});
     step(cb, sc<8>{});
+    if constexpr (BLOCKED) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          tot[i][j] += acc[i][j];
+          acc[i][j] = cb + 1 < NCB ? f32x4{0.f, 0.f, 0.f, 0.f} : tot[i][j];
+        }
+    }
   }
 
   // epilogue: conv1 -> relu -> out; downsample -> out2 (no relu), from registers

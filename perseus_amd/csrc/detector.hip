@@ -335,6 +335,29 @@ static int ensure_head(pa_detector* d, int B) {
 // Mode 2 (target = launch index): that launch is issued `reps` times back to back
 // between two events and nothing else is marked, so the average is free of the
 // inter-kernel event overhead (~5 us per launch in mode 1).
+// pa_detector_debug_tap: the maps of launch `index`, copied device to device on the forward's
+// stream around its PA_RUN site (in / res before the launch, out / out2 after it).  Each site
+// describes itself with PA_TAP first; only the tapped launch's description is kept.
+struct Tap {
+  pa_debug_tap* t;
+  int index;
+  bool hit = false;
+  hipError_t err = hipSuccess;
+  bool too_big = false;
+  const void *in = nullptr, *res = nullptr, *out = nullptr, *out2 = nullptr;
+  size_t in_b = 0, out_b = 0;
+  void copy(void* dst, const void* src, size_t n, size_t* copied, hipStream_t s) {
+    if (!dst || !src || !n) return;
+    if (n > t->cap) {
+      too_big = true;
+      return;
+    }
+    const hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) err = e;
+    *copied = n;
+  }
+};
+
 struct Prof {
   std::vector<hipEvent_t> ev;
   std::vector<const char*> names;
@@ -342,6 +365,7 @@ struct Prof {
   int target = -1, reps = 1, cur = 0;
   hipEvent_t t0 = nullptr, t1 = nullptr;
   const char* target_name = nullptr;
+  Tap* tap = nullptr;
   void record(const char* name) {
     hipEvent_t e;
     if (hipEventCreate(&e) != hipSuccess) return;
@@ -350,21 +374,63 @@ struct Prof {
     names.push_back(name);
   }
   void mark(const char* name) {
-    if (target < 0) record(name);
+    if (target < 0 && !tap) record(name);
   }
   int count() const { return (target == cur) ? reps : 1; }
+  bool tapped() const { return tap && tap->index == cur; }
   void before() {
     if (target == cur) hipEventRecord(t0, s);
+    if (tapped()) {
+      tap->copy(tap->t->in, tap->in, tap->in_b, &tap->t->in_bytes, s);
+      tap->copy(tap->t->res, tap->res, tap->out_b, &tap->t->res_bytes, s);
+    }
   }
   void after(const char* name) {
     if (target == cur) {
       hipEventRecord(t1, s);
       target_name = name;
     }
+    if (tapped()) {
+      tap->copy(tap->t->out, tap->out, tap->out_b, &tap->t->out_bytes, s);
+      tap->copy(tap->t->out2, tap->out2, tap->out_b, &tap->t->out2_bytes, s);
+      tap->t->name = name;
+      tap->hit = true;
+    }
     ++cur;
     mark(name);
   }
 };
+
+// describes the launch of the next PA_RUN site for pa_detector_debug_tap (es: bytes per map element)
+struct TapSite {
+  const void *in, *res, *out, *out2;
+  int conv, conv2, flags, B, Hin, Cin, Hout, Cout, ks, stride;
+};
+static void tap_site(Prof* prof, size_t es, const TapSite& k) {
+  Tap& p = *prof->tap;
+  pa_debug_tap& t = *p.t;
+  p.in = k.in;
+  p.res = k.res;
+  p.out = k.out;
+  p.out2 = k.out2;
+  const int hout = (k.flags & PA_TAP_MAXPOOL) && k.conv >= 0 ? k.Hout / 2 : k.Hout;  // the map the launch writes
+  p.in_b = (size_t)k.B * k.Hin * k.Hin * k.Cin * es;
+  p.out_b = (size_t)k.B * hout * hout * k.Cout * es;
+  t.conv = k.conv;
+  t.conv2 = k.conv2;
+  t.flags = k.flags;
+  t.B = k.B;
+  t.Hin = k.Hin;
+  t.Cin = k.Cin;
+  t.Hout = k.Hout;
+  t.Cout = k.Cout;
+  t.ks = k.ks;
+  t.stride = k.stride;
+}
+#define PA_TAP(es, ...)                                             \
+  do {                                                              \
+    if (prof && prof->tapped()) tap_site(prof, es, TapSite{__VA_ARGS__}); \
+  } while (0)
 
 // one timed launch site: runs `call` once (or `reps` times if it is the profiled target)
 #define PA_RUN(call, name)                                \
@@ -413,10 +479,14 @@ static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_
       PA_RUN(launch_stem_pool_rgbd(*rgbd, B, wts + st.w_off, d->bias + st.b_off, X, s), "stem_rgbd_conv7x7_pool");
     else if (rgb)  // RGB-only frames (3-channel models): crop or resize + crop in the row loads
       PA_RUN(launch_stem_pool_rgb(*rgb, B, wts + st.w_off, d->bias + st.b_off, X, s), "stem_rgb_conv7x7_pool");
-    else
+    else {
+      PA_TAP(sizeof(T), nullptr, nullptr, X, nullptr, 0, -1, PA_TAP_RELU | PA_TAP_MAXPOOL, B, 256, d->in_ch, 128, 64, 7, 2);
       PA_RUN(launch_stem_pool_fp16(x, B, d->in_ch, wts + st.w_off, d->bias + st.b_off, X, s), "stem_conv7x7_pool");
+    }
   } else {
+    PA_TAP(sizeof(T), nullptr, nullptr, S, nullptr, 0, -1, PA_TAP_RELU, B, 256, d->in_ch, 128, 64, 7, 2);
     PA_RUN(launch_stem<T>(x, B, d->in_ch, wts + st.w_off, d->bias + st.b_off, S, s), "stem_conv7x7");
+    PA_TAP(sizeof(T), S, nullptr, X, nullptr, -1, -1, PA_TAP_MAXPOOL, B, 128, 64, 64, 64, 3, 2);
     PA_RUN(launch_maxpool<T>(S, B, 128, 128, 64, X, s), "maxpool");
   }
   int hw = 64;
@@ -476,6 +546,7 @@ static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_
       sa.Wout = ho;
       sa.Cout = c1.cout;
       sa.trace = trace();
+      PA_TAP(sizeof(T), X, nullptr, Tb, D, b.conv1, b.ds, PA_TAP_RELU, B, hw, c1.cin, ho, c1.cout, 3, 2);
       bool small_s2 = false;
       if constexpr (std::is_same<T, _Float16>::value) small_s2 = small && g_variant[6] == 0 && ho != 16;
       if (small_s2) {
@@ -504,6 +575,7 @@ static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_
       a.pad = 1;
       a.epi = EPI_RELU;
       a.trace = trace();
+      PA_TAP(sizeof(T), X, nullptr, Tb, nullptr, b.conv1, -1, PA_TAP_RELU, B, hw, c1.cin, ho, c1.cout, 3, c1.stride);
       if (c1.stride == 1)
         PA_RUN(conv_s1(a, &kn), kn);
       else
@@ -516,6 +588,7 @@ static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_
         dsa.out = D;
         dsa.pad = 0;
         dsa.epi = 0;
+        PA_TAP(sizeof(T), X, nullptr, D, nullptr, b.ds, -1, 0, B, hw, cd.cin, ho, cd.cout, 1, c1.stride);
         PA_RUN(launch_conv<T>(dsa, 1, s, &kn), kn);
         res = D;
         out = D;
@@ -548,10 +621,13 @@ static int forward_t(pa_detector* d, const float* x, int B, float* y, hipStream_
       b2.fcb = d->fcb;
       b2.y = y;
     }
+    PA_TAP(sizeof(T), Tb, res, (b2.epi & EPI_HEAD) ? nullptr : out, nullptr, b.conv2, -1,
+           PA_TAP_RELU | PA_TAP_RES | ((b2.epi & EPI_HEAD) ? PA_TAP_HEAD : 0), B, ho, c2.cin, ho, c2.cout, 3, 1);
     PA_RUN(conv_s1(b2, &kn), kn);
     if (b.ds >= 0) std::swap(X, D);
     hw = ho;
   }
+  if (!fuse_head) PA_TAP(sizeof(T), X, nullptr, nullptr, nullptr, -1, -1, PA_TAP_HEAD, B, hw, 512, 1, 2 * d->n_kp, 1, 1);
   if (!fuse_head)
     PA_RUN(launch_head<T>(X, B, hw * hw, 512, d->fcw, d->fcb, 2 * d->n_kp, y, s, px, d->H, d->W), "avgpool_fc");
   else if (px)
@@ -593,6 +669,7 @@ static int forward_x3(pa_detector* d, const float* x, int B, float* y, hipStream
   _Float16* D = Tb + act_el;
   if (prof) prof->mark("start");
   const ConvL& st = d->convs[0];
+  PA_TAP(4, nullptr, nullptr, X, nullptr, 0, -1, PA_TAP_RELU | PA_TAP_MAXPOOL, B, 256, d->in_ch, 128, 64, 7, 2);
   if (small)
     PA_RUN(launch_stem_pool_x3_small(x, B, d->in_ch, d->w3 + st.w3_off, d->bstem3, d->scl + st.b_off, X, s),
            "stem_x3_conv7x7_pool_small");
@@ -656,6 +733,7 @@ static int forward_x3(pa_detector* d, const float* x, int B, float* y, hipStream
       sa.Cout = c1.cout;
       sa.part = d->part;
       sa.trace = trace();
+      PA_TAP(4, X, nullptr, Tb, D, b.conv1, b.ds, PA_TAP_RELU, B, hw, c1.cin, ho, c1.cout, 3, 2);
       if (small)
         PA_RUN(launch_conv3x3s2_small_x3(sa, s, &kn), kn);
       else
@@ -672,6 +750,7 @@ static int forward_x3(pa_detector* d, const float* x, int B, float* y, hipStream
       a.Cout = c1.cout;
       a.epi = EPI_RELU;
       a.trace = trace();
+      PA_TAP(4, X, nullptr, Tb, nullptr, b.conv1, -1, PA_TAP_RELU, B, hw, c1.cin, ho, c1.cout, 3, 1);
       PA_RUN(s1(a), kn);
     }
     ConvArgs b2 = a;
@@ -687,10 +766,12 @@ static int forward_x3(pa_detector* d, const float* x, int B, float* y, hipStream
     b2.Cout = c2.cout;
     b2.epi = EPI_RELU | EPI_RES;
     b2.trace = trace();
+    PA_TAP(4, Tb, res, out, nullptr, b.conv2, -1, PA_TAP_RELU | PA_TAP_RES, B, ho, c2.cin, ho, c2.cout, 3, 1);
     PA_RUN(s1(b2), kn);
     if (b.ds >= 0) std::swap(X, D);
     hw = ho;
   }
+  PA_TAP(4, X, nullptr, nullptr, nullptr, -1, -1, PA_TAP_HEAD, B, hw, 512, 1, 2 * d->n_kp, 1, 1);
   PA_RUN(launch_head_x3(X, B, hw * hw, 512, d->fcw, d->fcb, 2 * d->n_kp, y, s, px, d->H, d->W), "avgpool_fc_x3");
   return PA_OK;
 }
@@ -1053,6 +1134,24 @@ int pa_detector_time_launch(pa_detector* d, const float* x_dev, int B, float* y_
   hipEventDestroy(p.t0);
   hipEventDestroy(p.t1);
   return rc;
+}
+
+int pa_detector_debug_tap(pa_detector* d, const float* x_dev, int B, float* y_dev, void* stream, int index,
+                          pa_debug_tap* tap) {
+  PA_CHECK(tap && index >= 0, "tap: null tap or index %d", index);
+  PA_CHECK(B >= 1 && B <= pa::kChunk, "tap: batch %d not in [1, %d] (one chunk)", B, pa::kChunk);
+  tap->in_bytes = tap->res_bytes = tap->out_bytes = tap->out2_bytes = 0;
+  tap->name = nullptr;
+  pa::Tap t{tap, index};
+  pa::Prof p;
+  p.s = (hipStream_t)stream;
+  p.tap = &t;
+  const int rc = pa::forward(d, x_dev, B, y_dev, p.s, &p);
+  if (rc != PA_OK) return rc;
+  PA_CHECK(t.hit, "tap: launch index %d out of range (%d launches)", index, p.cur);
+  PA_CHECK(!t.too_big, "tap: a map of launch %d is larger than the %zu-byte buffers", index, tap->cap);
+  PA_CHECK(t.err == hipSuccess, "tap: hipMemcpyAsync: %s", hipGetErrorString(t.err));
+  return PA_OK;
 }
 
 int pa_detector_debug_set_trace(pa_detector* d, unsigned long long* trace_dev) {

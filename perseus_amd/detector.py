@@ -365,6 +365,64 @@ class KeypointCNN(nn.Module):
         return [(names[i].decode(), ms[i]) for i in range(n)], y
 
 
+    def tap(self, x: torch.Tensor, index: int, frames: "int | None" = None) -> dict:
+        """One launch of a normal forward with the maps it touched (pa_detector_debug_tap; launch
+        indices as profile() / time_launch(), stem = 0).  Returns a dict of the launch's side data
+        (`name`; `conv` / `conv2`: (conv, bn) state-dict prefixes of the convolution and of the fused
+        downsample, or None; `relu`, `residual`, `maxpool`, `head`; `B Hin Cin Hout Cout ks stride`),
+        `y` (the forward's keypoints, on the device), `native` (the maps as the library holds them,
+        on the device: "in", "res", "out", "out2" where the launch has them; NHWC fp16 / f32, fp16x3
+        (B, H, W, 2, C) fp16 with hi = [..., 0, :]; the stem's "in" is x, a head's "out" is y) and
+        `maps` (the same decoded to f64 NCHW on the CPU, fp16x3 as hi + lo; only the first `frames`
+        frames when given)."""
+        x, _ = self._prep(x)
+        dev = x.device
+        h = self._ensure_handle(dev)
+        L = _lib.lib()
+        _lib.check(L.pa_detector_set_precision(h, _lib.precision_code(self.precision)), "set_precision")
+        B = x.shape[0]
+        es = 2 if self.precision == "fp16" else 4
+        cap = B * 128 * 128 * 64 * 4 if self.precision == "fp32" else B * 64 * 64 * 64 * es
+        bufs = {k: torch.empty(cap, dtype=torch.uint8, device=dev) for k in ("in", "res", "out", "out2")}
+        y = torch.full((B, 2 * self.n_keypoints), float("nan"), dtype=torch.float32, device=dev)
+        t = _lib.DebugTap()
+        t.in_, t.res, t.out, t.out2 = (bufs[k].data_ptr() for k in ("in", "res", "out", "out2"))
+        t.cap = cap
+        with torch.cuda.device(dev):
+            _lib.check(L.pa_detector_debug_tap(h, x.data_ptr(), B, y.data_ptr(), _lib.stream_of(dev), index,
+                                               _lib.C.byref(t)), "pa_detector_debug_tap")
+        keys = conv_keys()
+        info = {"name": t.name.decode(), "conv": keys[t.conv] if t.conv >= 0 else None,
+                "conv2": keys[t.conv2] if t.conv2 >= 0 else None, "relu": bool(t.flags & _lib.TAP_RELU),
+                "residual": bool(t.flags & _lib.TAP_RES), "maxpool": bool(t.flags & _lib.TAP_MAXPOOL),
+                "head": bool(t.flags & _lib.TAP_HEAD), "y": y}
+        for k in ("B", "Hin", "Cin", "Hout", "Cout", "ks", "stride"):
+            info[k] = getattr(t, k)
+        dt = torch.float16 if es == 2 or self.precision == "fp16x3" else torch.float32
+        native = {}
+        for k, n in (("in", t.in_bytes), ("res", t.res_bytes), ("out", t.out_bytes), ("out2", t.out2_bytes)):
+            if not n:
+                continue
+            ch = t.Cin if k == "in" else t.Cout
+            hw = int(round((n // (B * ch * es)) ** 0.5))  # square maps
+            tail = (2, ch) if self.precision == "fp16x3" else (ch,)
+            native[k] = bufs[k][:n].view(dt).view(B, hw, hw, *tail)
+        if t.conv == 0:
+            native["in"] = x
+        if info["head"]:
+            native["out"] = y
+        nf = B if frames is None else min(frames, B)
+        maps = {}
+        for k, a in native.items():
+            a = a[:nf].cpu().double()
+            if a.dim() == 5:
+                a = a.sum(3)  # hi + lo (exact in f64)
+            nhwc = a.dim() == 4 and not (k == "in" and t.conv == 0)  # (x is NCHW already, y is (B, 2K))
+            maps[k] = a.permute(0, 3, 1, 2).contiguous() if nhwc else a
+        info["native"] = native
+        info["maps"] = maps
+        return info
+
     def time_launch(self, x: torch.Tensor, index: int, reps: int = 20):
         """(name, avg ms) of launch `index` of the forward, issued `reps` times back to
         back between two HIP events on the current stream (no per-launch event gaps)."""
@@ -382,6 +440,19 @@ class KeypointCNN(nn.Module):
                                                  index, reps, _lib.C.byref(ms), _lib.C.byref(name)),
                        "pa_detector_time_launch")
         return name.value.decode(), ms.value
+
+
+def conv_keys() -> list:
+    """(conv, bn) state-dict prefixes of the convolutions in weight-blob order: the indices
+    `pa_debug_tap.conv / .conv2` use (0 = stem; per block conv1, conv2, then its downsample)."""
+    keys = [("resnet.conv1", "resnet.bn1")]
+    for li in range(1, 5):
+        for bi in range(2):
+            p = f"resnet.layer{li}.{bi}"
+            keys += [(p + ".conv1", p + ".bn1"), (p + ".conv2", p + ".bn2")]
+            if li > 1 and bi == 0:
+                keys.append((p + ".downsample.0", p + ".downsample.1"))
+    return keys
 
 
 def denormalize_pixel_coordinates(y: torch.Tensor, H: int = 256, W: int = 256, target: torch.Tensor | None = None):
