@@ -437,6 +437,85 @@ int pa_window_pose_tick_post(const pa_traj_args* args, const float* y_new_dev, c
  * pa_window_lm_solve (newest_pending) it prepares the post half for the solved window. */
 int pa_window_pose_tick_reduce(const pa_traj_args* args, double lambda, void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------- fixed-lag marginalization
+ * What GTSAM's BatchFixedLagSmoother / IncrementalFixedLagSmoother do when the oldest state leaves
+ * the lag: it is marginalized, and the Schur complement of its factors stays behind as a linear
+ * prior on the state that is now oldest (a LinearContainerFactor with its linearization point),
+ * instead of pa_window_advance simply forgetting frame 0.
+ * The prior is held per trajectory, f64, on the device, in INFORMATION form (the marginal is only
+ * positive semi-definite -- frame 1's angular velocity gets no information from frame 0 -- so a
+ * square root would not exist):
+ *   info (T, 12, 12) row-major, the symmetric Lambda over the frame block [pose tangent 6 |
+ *   angvel 3 | vel 3] in pa_window_retract's chart;  eta (T, 12);  xbar_pose (T, 12), xbar_angvel
+ *   (T, 3), xbar_vel (T, 3): the state it was linearized at.
+ * With xi = [Logmap(xbar_pose^-1 pose); angvel - xbar_angvel; vel - xbar_vel] the prior's cost is
+ * 0.5 xi^T Lambda xi - eta^T xi.  As LinearContainerFactor does, Lambda is kept fixed and the
+ * chart's Jacobian is taken as the identity, so at a state x the prior contributes
+ *   D_0 += Lambda,  g_0 += Lambda xi - eta
+ * to the normal equations of pa_trajectory_gn_step (frame 0's blocks).
+ *
+ * pa_window_prior_linearize: xi of window frame `frame` (0 <= frame < L; pose (T*L, 12), angvel,
+ * vel (T*L, 3)) against xbar, grad (T, 12) = Lambda xi - eta and err (T) or NULL = 0.5 xi^T Lambda xi
+ * - eta^T xi.  One launch, no host synchronisation. */
+int pa_window_prior_linearize(int T, int L, int frame, const double* info, const double* eta,
+                              const double* xbar_pose, const double* xbar_angvel, const double* xbar_vel,
+                              const double* pose, const double* angvel, const double* vel, double* grad_out,
+                              double* err_out, void* stream);
+
+/* pa_window_marginalize: marginalizes frame 0 of every trajectory's window, from the WHITENED
+ * factor outputs pa_trajectory_gn_step takes (same layouts and null rules; status != 0 skipped)
+ * and the prior the window carried so far (prior_info_in (T, 12, 12), prior_grad_in (T, 12): its
+ * gradient at the factors' linearization point; both NULL = no prior yet):
+ *   H = D_0 + Lambda_in + lambda I,   F = B^T B,  h = B^T r  (B: the x_1 part of the dynamics and
+ *   constant-velocity factors (0, 1), r their residuals),
+ *   Lambda' = F - E_0^T H^-1 E_0  (exactly symmetric),   g' = h - E_0^T H^-1 (g_0 + grad_in).
+ * delta (T*L, 12) or NULL with gn_info (T) or NULL: the step the window was retracted by after the
+ * factors were linearized; where given and gn_info[t] == 0 (or gn_info NULL), the prior is
+ * re-centred to first order at the retracted state, g' += Lambda' delta[t, frame 1].
+ * Outputs: info_out = Lambda', eta_out = -g', xbar_* = window frame 1's state (pose (T*L, 12),
+ * angvel, vel (T*L, 3)) as it stands, and minfo (T): 0 = computed; 1 = H not positive definite;
+ * 2 = nvalid[t] < L (nvalid (T) or NULL: the window is not full, frame 0 is a copy of the initial
+ * guess and no measurement).  In both non-zero cases the new prior is zero (xbar still written).
+ * Solving frames 1..L-1's own factors with this prior on frame 1 gives the delta that solving
+ * all L frames with the input prior gives for them (the Schur complement identity).
+ * T >= 0 (0 is a no-op), L >= 2, 0 <= n_kp <= 16, lambda >= 0; everything else returns PA_EINVAL
+ * before any launch.  One launch, one workgroup per trajectory, no host synchronisation. */
+int pa_window_marginalize(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                          const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                          const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
+                          const double* j_cv0, const double* j_cv1, const double* prior_info_in,
+                          const double* prior_grad_in, double lambda, const double* delta, const int32_t* gn_info,
+                          const int32_t* nvalid, const double* pose, const double* angvel, const double* vel,
+                          double* info_out, double* eta_out, double* xbar_pose_out, double* xbar_angvel_out,
+                          double* xbar_vel_out, int32_t* minfo, void* stream);
+
+/* pa_trajectory_gn_step / pa_trajectory_marginals and the streaming ticks with the prior on
+ * frame 0: the parent plus prior_info (T, 12, 12) and prior_grad (T, 12), given together; both NULL
+ * is the parent, bit for bit.  (pa_traj_args itself is unchanged: the prior travels beside it.
+ * pa_window_pose_tick_post needs no sibling, the prior is in the system the pre half reduced.)
+ * pa_trajectory_lm_solve and pa_window_lm_solve have no such sibling and so take no prior: their
+ * cost would need the prior's err and a re-linearization per iteration. */
+int pa_trajectory_gn_step_prior(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                                const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                                const double* j_dyn1, const double* j_dyn2, const double* j_dyn3,
+                                const double* r_cv, const double* j_cv0, const double* j_cv1, double lambda,
+                                double* D, double* E, double* g, double* delta, int32_t* info, void* ws,
+                                size_t ws_bytes, const double* prior_info, const double* prior_grad, void* stream);
+int pa_trajectory_marginals_prior(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                                  const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                                  const double* j_dyn1, const double* j_dyn2, const double* j_dyn3,
+                                  const double* r_cv, const double* j_cv0, const double* j_cv1, double lambda,
+                                  double* cov, double* cross, double* cov_newest, int32_t* info, void* ws,
+                                  size_t ws_bytes, const double* prior_info, const double* prior_grad,
+                                  void* stream);
+int pa_window_pose_tick_prior(const pa_traj_args* args, const float* y_new_dev, double lambda, double* delta_dev,
+                              int32_t* info_dev, double* newest_pose_dev, const double* prior_info,
+                              const double* prior_grad, void* stream);
+int pa_window_pose_tick_pre_prior(const pa_traj_args* args, double lambda, void* ws_dev, size_t ws_bytes,
+                                  const double* prior_info, const double* prior_grad, void* stream);
+int pa_window_pose_tick_reduce_prior(const pa_traj_args* args, double lambda, void* ws_dev, size_t ws_bytes,
+                                     const double* prior_info, const double* prior_grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

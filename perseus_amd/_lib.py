@@ -113,6 +113,18 @@ _SIGS = {
     "pa_trajectory_marginals_workspace": (C.c_size_t, [C.c_int, C.c_int]),
     "pa_trajectory_marginals": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_double]
                                 + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
+    "pa_trajectory_gn_step_prior": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_double]
+                                    + [C.c_void_p] * 6 + [C.c_size_t] + [C.c_void_p] * 3),
+    "pa_trajectory_marginals_prior": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_double]
+                                      + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 3),
+    "pa_window_pose_tick_prior": (C.c_int, [C.POINTER(TrajArgs), C.c_void_p, C.c_double] + [C.c_void_p] * 6),
+    "pa_window_pose_tick_pre_prior": (C.c_int, [C.POINTER(TrajArgs), C.c_double, C.c_void_p, C.c_size_t]
+                                      + [C.c_void_p] * 3),
+    "pa_window_pose_tick_reduce_prior": (C.c_int, [C.POINTER(TrajArgs), C.c_double, C.c_void_p, C.c_size_t]
+                                         + [C.c_void_p] * 3),
+    "pa_window_prior_linearize": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
+    "pa_window_marginalize": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13 + [C.c_double]
+                              + [C.c_void_p] * 13),
     "pa_window_advance": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double, C.c_int,
                                                                                      C.c_void_p]),
     "pa_window_advance_n": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double, C.c_int,

@@ -25,13 +25,17 @@ struct GnArgs {
   int32_t* info;
   double* ws;
   unsigned long long* trace;  // timing only (pa_debug_gn_set_trace): 256 s_memrealtime stamps per trajectory
+  // the marginalization prior on frame 0 (prior.hip): Lambda (T, 12, 12) and its gradient
+  // Lambda xi - eta (T, 12), added to D_0 / g_0 by gn_build_frame; null = no prior
+  const double *p_info, *p_grad;
 };
 
 // the step on the factor set s (delta only: no D / E / g outputs, no trace)
 __host__ __device__ __forceinline__ GnArgs gn_args(int T, int L, int K, const FactorSet& s, double lambda,
                                                    double* delta, int32_t* info, double* ws) {
   return GnArgs{T,      L,        K,        s.r_proj, s.j_proj, s.status, s.r_dyn, s.j_dyn0, s.j_dyn1, s.j_dyn2, s.j_dyn3,
-                s.r_cv, s.j_cv0,  s.j_cv1,  lambda,   nullptr,  nullptr,  nullptr, delta,    info,     ws,       nullptr};
+                s.r_cv, s.j_cv0,  s.j_cv1,  lambda,   nullptr,  nullptr,  nullptr, delta,    info,     ws,       nullptr,
+                nullptr, nullptr};
 }
 // ... on the factor outputs ta names
 inline GnArgs gn_args(const pa_traj_args& ta, double lambda, double* delta, int32_t* info, double* ws) {
@@ -338,6 +342,20 @@ __device__ __forceinline__ void gn_build_frame(const GnArgs& a, long f, const Gn
         const double bt = li < NV ? BT[li][row] : 0.0;
         cE = __builtin_amdgcn_mfma_f64_16x16x4f64(an, bt, cE, 0, 0, 0);
       }
+    }
+  }
+  // the marginalization prior on the oldest frame: D_0 += Lambda, g_0 += Lambda xi - eta (the
+  // branch is uniform; without a prior nothing here changes cD)
+  if (l == 0 && a.p_info != nullptr) {
+    const double* pi = a.p_info + (size_t)t * NB;
+    const double* pg = a.p_grad + (size_t)t * NV;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {  // rows lk + 4v < 12
+      const int i = lk + 4 * v;
+      if (li < NV)
+        cD[v] += pi[i * NV + li];
+      else if (li == NV)
+        cD[v] += pg[i];
     }
   }
   // D / E / g go to the API outputs only when the caller asked for them (a.D null: the

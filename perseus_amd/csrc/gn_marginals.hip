@@ -209,11 +209,13 @@ size_t pa_trajectory_marginals_workspace(int T, int L) {
   return (T > 0 && L > 0) ? (size_t)T * L * pa::MG_WSF * sizeof(double) : 0;
 }
 
-int pa_trajectory_marginals(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
-                            const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
-                            const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
-                            const double* j_cv0, const double* j_cv1, double lambda, double* cov, double* cross,
-                            double* cov_newest, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+// pa_trajectory_marginals with the marginalization prior on frame 0 (prior_info / prior_grad null: none, the parent)
+int pa_trajectory_marginals_prior(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                          const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                          const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
+                          const double* j_cv0, const double* j_cv1, double lambda, double* cov, double* cross,
+                          double* cov_newest, int32_t* info, void* ws, size_t ws_bytes, const double* prior_info,
+                          const double* prior_grad, void* stream) {
   PA_CHECK(T >= 0 && L >= 2 && n_kp >= 0 && n_kp <= pa::GN_KMAX, "marginals: T %d L %d (>= 2) n_kp %d (<= %d)", T, L,
            n_kp, pa::GN_KMAX);
   if (T == 0) return PA_OK;
@@ -221,13 +223,15 @@ int pa_trajectory_marginals(int T, int L, int n_kp, const double* r_proj, const 
   PA_CHECK(cov || cov_newest, "marginals: null cov and cov_newest (one of them is required)");
   PA_CHECK(!cross || cov, "marginals: cross is given with cov only");
   PA_CHECK(info && ws, "marginals: null info / workspace pointer");
+  PA_CHECK(!prior_info == !prior_grad, "marginals: prior_info and prior_grad are given together (or both NULL)");
   PA_CHECK(n_kp == 0 || (r_proj && j_proj), "marginals: null projection factors");
   PA_CHECK(r_dyn && j_dyn0 && j_dyn1 && j_dyn2 && j_dyn3 && r_cv && j_cv0 && j_cv1,
            "marginals: null dynamics / constant-velocity factors (Jacobians are required)");
   PA_CHECK(ws_bytes >= pa_trajectory_marginals_workspace(T, L), "marginals: workspace %zu < %zu", ws_bytes,
            pa_trajectory_marginals_workspace(T, L));
   const pa::GnArgs a{T,     L,     n_kp,  r_proj, j_proj,  status_proj, r_dyn,   j_dyn0,  j_dyn1, j_dyn2,      j_dyn3,
-                     r_cv,  j_cv0, j_cv1, lambda, nullptr, nullptr,     nullptr, nullptr, info,   (double*)ws, nullptr};
+                     r_cv,  j_cv0, j_cv1, lambda, nullptr, nullptr,     nullptr, nullptr, info,   (double*)ws, nullptr,
+                     prior_info, prior_grad};
   const hipStream_t s = (hipStream_t)stream;
   pa::gn_for_kp(n_kp, [&](auto rp) {
     hipLaunchKernelGGL(pa::gn_marginals_kernel<decltype(rp)::value>, dim3(T), dim3(128), 0, s, a, cov, cross,
@@ -235,6 +239,15 @@ int pa_trajectory_marginals(int T, int L, int n_kp, const double* r_proj, const 
   });
   PA_LAUNCH_CHECK();
   return PA_OK;
+}
+
+int pa_trajectory_marginals(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                            const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                            const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
+                            const double* j_cv0, const double* j_cv1, double lambda, double* cov, double* cross,
+                            double* cov_newest, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+  return pa_trajectory_marginals_prior(T, L, n_kp, r_proj, j_proj, status_proj, r_dyn, j_dyn0, j_dyn1, j_dyn2, j_dyn3, r_cv, j_cv0,
+                        j_cv1, lambda, cov, cross, cov_newest, info, ws, ws_bytes, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

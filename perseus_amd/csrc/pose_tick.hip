@@ -239,20 +239,32 @@ static void launch_lin(const pa_traj_args* ta, const float* y_new, hipStream_t s
 }
 
 // the cyclic reduction in the ROOT order into the tick workspace (the pre half's second launch)
-static void launch_pre(const pa_traj_args* ta, double lambda, void* ws, hipStream_t s) {
-  const pa::GnArgs g = pa::gn_args(*ta, lambda, nullptr, nullptr, (double*)ws);
+static void launch_pre(const pa_traj_args* ta, double lambda, void* ws, const double* pi, const double* pg,
+                       hipStream_t s) {
+  pa::GnArgs g = pa::gn_args(*ta, lambda, nullptr, nullptr, (double*)ws);
+  g.p_info = pi;
+  g.p_grad = pg;
   pa::gn_for_kp(ta->n_kp, [&](auto rp) {
     hipLaunchKernelGGL(pa::pose_tick_pre_kernel<decltype(rp)::value>, dim3(ta->T), dim3(64 * pa::GN_CR_W), 0, s, g);
   });
 }
 
-int pa_window_pose_tick(const pa_traj_args* ta, const float* y_new, double lambda, double* delta, int32_t* info,
-                        double* newest_pose, void* stream) {
+// the marginalization prior on frame 0 (prior.hip), given together or not at all
+static int prior_pair_check(const double* pi, const double* pg, const char* who) {
+  PA_CHECK(!pi == !pg, "%s: prior_info and prior_grad are given together (or both NULL)", who);
+  return PA_OK;
+}
+
+int pa_window_pose_tick_prior(const pa_traj_args* ta, const float* y_new, double lambda, double* delta, int32_t* info,
+                              double* newest_pose, const double* prior_info, const double* prior_grad, void* stream) {
   PA_CHECK(ta && y_new && delta && info, "pose tick: null args / y_new / delta / info");
-  const int rc = pose_tick_check(ta, lambda, "pose tick");
+  int rc = pose_tick_check(ta, lambda, "pose tick");
   if (rc != PA_OK || ta->T == 0) return rc;
+  if ((rc = prior_pair_check(prior_info, prior_grad, "pose tick")) != PA_OK) return rc;
   const int T = ta->T;
-  const pa::GnArgs g = pa::gn_args(*ta, lambda, delta, info, nullptr);
+  pa::GnArgs g = pa::gn_args(*ta, lambda, delta, info, nullptr);
+  g.p_info = prior_info;
+  g.p_grad = prior_grad;
   const hipStream_t s = (hipStream_t)stream;
   if (!(pa::g_gn_na & 2048)) launch_lin(ta, y_new, s);
   if (pa::g_gn_na & 1024) { PA_LAUNCH_CHECK(); return PA_OK; }
@@ -267,24 +279,41 @@ int pa_window_pose_tick(const pa_traj_args* ta, const float* y_new, double lambd
   return PA_OK;
 }
 
-int pa_window_pose_tick_pre(const pa_traj_args* ta, double lambda, void* ws, size_t ws_bytes, void* stream) {
+int pa_window_pose_tick(const pa_traj_args* ta, const float* y_new, double lambda, double* delta, int32_t* info,
+                        double* newest_pose, void* stream) {
+  return pa_window_pose_tick_prior(ta, y_new, lambda, delta, info, newest_pose, nullptr, nullptr, stream);
+}
+
+int pa_window_pose_tick_pre_prior(const pa_traj_args* ta, double lambda, void* ws, size_t ws_bytes,
+                                  const double* prior_info, const double* prior_grad, void* stream) {
   int rc = pose_tick_check(ta, lambda, "pose tick pre");
   if (rc != PA_OK || ta->T == 0) return rc;
+  if ((rc = prior_pair_check(prior_info, prior_grad, "pose tick pre")) != PA_OK) return rc;
   if ((rc = pose_tick_ws_check(ta, ws, ws_bytes, "pose tick pre")) != PA_OK) return rc;
   const hipStream_t s = (hipStream_t)stream;
   launch_lin(ta, nullptr, s);
-  launch_pre(ta, lambda, ws, s);
+  launch_pre(ta, lambda, ws, prior_info, prior_grad, s);
+  PA_LAUNCH_CHECK();
+  return PA_OK;
+}
+
+int pa_window_pose_tick_pre(const pa_traj_args* ta, double lambda, void* ws, size_t ws_bytes, void* stream) {
+  return pa_window_pose_tick_pre_prior(ta, lambda, ws, ws_bytes, nullptr, nullptr, stream);
+}
+
+int pa_window_pose_tick_reduce_prior(const pa_traj_args* ta, double lambda, void* ws, size_t ws_bytes,
+                                     const double* prior_info, const double* prior_grad, void* stream) {
+  int rc = pose_tick_check(ta, lambda, "pose tick reduce");
+  if (rc != PA_OK || ta->T == 0) return rc;
+  if ((rc = prior_pair_check(prior_info, prior_grad, "pose tick reduce")) != PA_OK) return rc;
+  if ((rc = pose_tick_ws_check(ta, ws, ws_bytes, "pose tick reduce")) != PA_OK) return rc;
+  launch_pre(ta, lambda, ws, prior_info, prior_grad, (hipStream_t)stream);
   PA_LAUNCH_CHECK();
   return PA_OK;
 }
 
 int pa_window_pose_tick_reduce(const pa_traj_args* ta, double lambda, void* ws, size_t ws_bytes, void* stream) {
-  int rc = pose_tick_check(ta, lambda, "pose tick reduce");
-  if (rc != PA_OK || ta->T == 0) return rc;
-  if ((rc = pose_tick_ws_check(ta, ws, ws_bytes, "pose tick reduce")) != PA_OK) return rc;
-  launch_pre(ta, lambda, ws, (hipStream_t)stream);
-  PA_LAUNCH_CHECK();
-  return PA_OK;
+  return pa_window_pose_tick_reduce_prior(ta, lambda, ws, ws_bytes, nullptr, nullptr, stream);
 }
 
 int pa_window_pose_tick_post(const pa_traj_args* ta, const float* y_new, const void* ws, size_t ws_bytes,

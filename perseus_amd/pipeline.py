@@ -152,13 +152,15 @@ class GNPlan:
     (the streaming pose stage).  out: delta (T*L,12), info (T,) int32 (0 = solved), and
     with blocks=True also the normal-matrix blocks D (T*L,12,12), E (T*(L-1),12,12) and
     g (T*L,12) (blocks=False: they stay on chip, the launch writes delta and info only).
-    Variable block per frame: [pose (6) | angvel (3) | vel (3)]."""
+    Variable block per frame: [pose (6) | angvel (3) | vel (3)].
+    prior (optional, a PriorPlan): the marginalization prior on frame 0, its current Lambda and
+    the gradient its last linearize() left (pa_trajectory_gn_step_prior)."""
 
-    def __init__(self, lin: dict, *, T: int, L: int, lam: float = 0.0, blocks: bool = False):
+    def __init__(self, lin: dict, *, T: int, L: int, lam: float = 0.0, blocks: bool = False, prior=None):
         if lin.get("j_proj") is None:
             raise RuntimeError("gn_step needs the Jacobians (linearize with jacobians=True)")
         dev = lin["r_proj"].device
-        self.T, self.L, self.lam, self.lin = T, L, float(lam), lin
+        self.T, self.L, self.lam, self.lin, self.prior = T, L, float(lam), lin, prior
         self.n_kp = lin["r_proj"].shape[0] // (T * L) if T * L else 0
         m = T * max(L - 1, 0)
         self.m = m
@@ -177,12 +179,16 @@ class GNPlan:
         """One pa_trajectory_gn_step on the device's current stream."""
         lin, out, p = self.lin, self.out, _lib.ptr
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib().pa_trajectory_gn_step(
-                self.T, self.L, self.n_kp, p(lin["r_proj"]), p(lin["j_proj"]), p(lin.get("status")), p(lin["r_dyn"]),
-                p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]), p(lin["r_cv"]),
-                p(lin["j_cv0"]), p(lin["j_cv1"]), self.lam, p(out.get("D")), p(out.get("E")), p(out.get("g")),
-                p(out["delta"]),
-                p(out["info"]), p(self.ws), self.ws.numel(), _lib.stream_of(self.dev)), "pa_trajectory_gn_step")
+            args = (self.T, self.L, self.n_kp, p(lin["r_proj"]), p(lin["j_proj"]), p(lin.get("status")),
+                    p(lin["r_dyn"]), p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]),
+                    p(lin["r_cv"]), p(lin["j_cv0"]), p(lin["j_cv1"]), self.lam, p(out.get("D")), p(out.get("E")),
+                    p(out.get("g")), p(out["delta"]), p(out["info"]), p(self.ws), self.ws.numel())
+            if self.prior is None:
+                _lib.check(_lib.lib().pa_trajectory_gn_step(*args, _lib.stream_of(self.dev)), "pa_trajectory_gn_step")
+            else:
+                _lib.check(_lib.lib().pa_trajectory_gn_step_prior(*args, p(self.prior.info), p(self.prior.grad),
+                                                                  _lib.stream_of(self.dev)),
+                           "pa_trajectory_gn_step_prior")
 
 
 def gn_step(lin: dict, *, T: int, L: int, lam: float = 0.0) -> dict:
@@ -209,10 +215,12 @@ class MarginalsPlan:
     cross (T*(L-1),12,12) = Sigma_{l,l+1}, frame l on rows; newest=True: cov_newest (T,12,12),
     bit for bit cov's last block per trajectory (alone, only the forward elimination runs).
     lam = 0 fails on a full window (the last frame's angular velocity is in no factor): pass a
-    small lam (1e-9) for the undamped covariance."""
+    small lam (1e-9) for the undamped covariance.
+    prior (optional, a PriorPlan): the marginalization prior on frame 0; its current Lambda joins
+    frame 0's block (pa_trajectory_marginals_prior)."""
 
     def __init__(self, lin: dict, *, T: int, L: int, lam: float, full: bool = True, cross: bool = False,
-                 newest: bool = False):
+                 newest: bool = False, prior=None):
         if lin.get("j_proj") is None:
             raise RuntimeError("marginals needs the Jacobians (linearize with jacobians=True)")
         if not (full or newest):
@@ -220,7 +228,7 @@ class MarginalsPlan:
         if cross and not full:
             raise ValueError("MarginalsPlan: cross=True needs full=True")
         dev = lin["r_proj"].device
-        self.T, self.L, self.lam, self.lin, self.dev = T, L, float(lam), lin, dev
+        self.T, self.L, self.lam, self.lin, self.dev, self.prior = T, L, float(lam), lin, dev, prior
         self.n_kp = lin["r_proj"].shape[0] // (T * L) if T * L else 0
 
         def e(*shape, dtype=torch.float64):
@@ -240,12 +248,17 @@ class MarginalsPlan:
         """One pa_trajectory_marginals on the device's current stream."""
         lin, out, p = self.lin, self.out, _lib.ptr
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib().pa_trajectory_marginals(
-                self.T, self.L, self.n_kp, p(lin["r_proj"]), p(lin["j_proj"]), p(lin.get("status")), p(lin["r_dyn"]),
-                p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]), p(lin["r_cv"]),
-                p(lin["j_cv0"]), p(lin["j_cv1"]), self.lam, p(out.get("cov")), p(out.get("cross")),
-                p(out.get("cov_newest")), p(out["info"]), p(self.ws), self.ws.numel(), _lib.stream_of(self.dev)),
-                "pa_trajectory_marginals")
+            args = (self.T, self.L, self.n_kp, p(lin["r_proj"]), p(lin["j_proj"]), p(lin.get("status")),
+                    p(lin["r_dyn"]), p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]),
+                    p(lin["r_cv"]), p(lin["j_cv0"]), p(lin["j_cv1"]), self.lam, p(out.get("cov")), p(out.get("cross")),
+                    p(out.get("cov_newest")), p(out["info"]), p(self.ws), self.ws.numel())
+            if self.prior is None:
+                _lib.check(_lib.lib().pa_trajectory_marginals(*args, _lib.stream_of(self.dev)),
+                           "pa_trajectory_marginals")
+            else:
+                _lib.check(_lib.lib().pa_trajectory_marginals_prior(*args, p(self.prior.info), p(self.prior.grad),
+                                                                    _lib.stream_of(self.dev)),
+                           "pa_trajectory_marginals_prior")
 
 
 def marginals(lin: dict, *, T: int, L: int, lam: float, cross: bool = False) -> dict:
@@ -257,6 +270,86 @@ def marginals(lin: dict, *, T: int, L: int, lam: float, cross: bool = False) -> 
     out = dict(plan.out)
     out["_ws"] = plan.ws
     return out
+
+
+class PriorPlan:
+    """The fixed-lag marginalization prior of T trajectory windows (include/perseus_amd.h "fixed-lag
+    marginalization"): what GTSAM's BatchFixedLagSmoother keeps of the states that left the lag,
+    a linear prior on the oldest frame, instead of the window forgetting them.  Buffers (device,
+    f64, allocated once so both launches can be captured in a HIP graph): the CURRENT prior info
+    (T,12,12), eta (T,12), xbar_pose (T,12), xbar_angvel / xbar_vel (T,3); the NEXT one (`nxt`,
+    the same keys) that marginalize() writes; grad (T,12) and err (T,) of linearize(); minfo (T,)
+    int32 of marginalize() (0 computed, 1 H not positive definite, 2 window not full: the next
+    prior is then zero).  A new plan holds the zero prior (no information)."""
+
+    def __init__(self, *, T: int, L: int, device):
+        self.T, self.L, self.dev = T, L, torch.device(device)
+
+        def z(*shape, dtype=torch.float64):
+            return torch.zeros(shape, dtype=dtype, device=self.dev)
+
+        def buf():  # one allocation per prior, so advance() is one copy
+            flat = z(T * 174)
+            b, o = {"_flat": flat}, 0
+            for k, shape in (("info", (T, 12, 12)), ("eta", (T, 12)), ("xbar_pose", (T, 12)), ("xbar_angvel", (T, 3)),
+                             ("xbar_vel", (T, 3))):
+                n = int(np.prod(shape))
+                b[k] = flat[o:o + n].view(shape)
+                o += n
+            b["xbar_pose"][:, (0, 4, 8)] = 1.0  # identity rotation
+            return b
+
+        self.cur, self.nxt = buf(), buf()
+        self.grad, self.err, self.minfo = z(T, 12), z(T), z(T, dtype=torch.int32)
+
+    @property
+    def info(self):
+        return self.cur["info"]
+
+    def zero(self) -> None:
+        """Back to the zero prior (current stream); xbar too goes back to the identity, so that
+        whatever state an earlier marginalization copied there (a NaN would survive the product
+        with a zero Lambda) is gone."""
+        for b in (self.cur, self.nxt):
+            b["_flat"].zero_()
+            b["xbar_pose"][:, (0, 4, 8)] = 1.0
+        self.grad.zero_()
+        self.err.zero_()
+        self.minfo.zero_()
+
+    def linearize(self, pose, angvel, vel, *, frame: int) -> None:
+        """pa_window_prior_linearize on the current stream: grad, err of the current prior at
+        window frame `frame` of pose (T*L,12) / angvel / vel (T*L,3)."""
+        p, c = _lib.ptr, self.cur
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().pa_window_prior_linearize(
+                self.T, self.L, int(frame), p(c["info"]), p(c["eta"]), p(c["xbar_pose"]), p(c["xbar_angvel"]),
+                p(c["xbar_vel"]), p(pose), p(angvel), p(vel), p(self.grad), p(self.err), _lib.stream_of(self.dev)),
+                "pa_window_prior_linearize")
+
+    def marginalize(self, lin: dict, pose, angvel, vel, *, lam: float, delta=None, gn_info=None, nvalid=None,
+                    n_kp: int | None = None) -> None:
+        """pa_window_marginalize on the current stream: frame 0 of the whitened factors `lin`,
+        with the current prior and the gradient linearize() left, becomes the NEXT prior (on
+        frame 1, xbar = frame 1 of pose / angvel / vel as they stand); delta (T*L,12) with gn_info:
+        the step the window was retracted by since `lin` was linearized.  advance() then makes
+        the next prior the current one."""
+        p, c, n = _lib.ptr, self.cur, self.nxt
+        if n_kp is None:
+            n_kp = lin["r_proj"].shape[0] // (self.T * self.L) if self.T * self.L and lin.get("r_proj") is not None else 0
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().pa_window_marginalize(
+                self.T, self.L, n_kp, p(lin.get("r_proj")), p(lin.get("j_proj")), p(lin.get("status")), p(lin["r_dyn"]),
+                p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]), p(lin["r_cv"]),
+                p(lin["j_cv0"]), p(lin["j_cv1"]), p(c["info"]), p(self.grad), float(lam), p(delta), p(gn_info),
+                p(nvalid), p(pose), p(angvel), p(vel), p(n["info"]), p(n["eta"]), p(n["xbar_pose"]),
+                p(n["xbar_angvel"]), p(n["xbar_vel"]), p(self.minfo), _lib.stream_of(self.dev)),
+                "pa_window_marginalize")
+
+    def advance(self) -> None:
+        """The next prior becomes the current one: one device copy on the current stream (capturable;
+        the buffers keep their addresses, so a captured graph and pa_traj_args stay valid)."""
+        self.cur["_flat"].copy_(self.nxt["_flat"])
 
 
 LM_DEFAULTS = dict(max_iters=30, lambda0=1e-3, lambda_up=10.0, lambda_down=10.0, lambda_min=1e-12, lambda_max=1e12,
@@ -365,17 +458,23 @@ def window_advance(y_new: torch.Tensor, win: dict, *, dt: float, vel_frame: str 
 TICK_MAX_L = 24  # pa_window_pose_tick: L <= 24 (the cyclic-reduction GN step), T <= the CU count
 
 
+def _prior_ptrs(prior):
+    """(prior_info, prior_grad) of a PriorPlan for the _prior entry points; (None, None) = the parent."""
+    return (None, None) if prior is None else (prior.info.data_ptr(), prior.grad.data_ptr())
+
+
 def window_pose_tick(args, y_new: torch.Tensor, *, lam: float, delta: torch.Tensor, info: torch.Tensor,
-                     newest: torch.Tensor | None = None) -> None:
+                     newest: torch.Tensor | None = None, prior=None) -> None:
     """pa_window_pose_tick on the device's current stream: window_advance(y_new) ->
     pa_trajectory_linearize(args) -> pa_trajectory_gn_step (delta, info) ->
     window_retract(newest) in two launches, bit for bit that sequence.  `args` comes from
-    prepare_trajectories over the window arrays (with nvalid, whitening sigmas and Jacobians)."""
+    prepare_trajectories over the window arrays (with nvalid, whitening sigmas and Jacobians).
+    prior (a PriorPlan): the marginalization prior on frame 0 in the GN step (pa_window_pose_tick_prior)."""
     dev = y_new.device
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().pa_window_pose_tick(C.byref(args), y_new.data_ptr(), float(lam), delta.data_ptr(),
-                                                  info.data_ptr(), _lib.ptr(newest), _lib.stream_of(dev)),
-                   "pa_window_pose_tick")
+        _lib.check(_lib.lib().pa_window_pose_tick_prior(C.byref(args), y_new.data_ptr(), float(lam), delta.data_ptr(),
+                                                        info.data_ptr(), _lib.ptr(newest), *_prior_ptrs(prior),
+                                                        _lib.stream_of(dev)), "pa_window_pose_tick")
 
 
 def window_pose_tick_workspace(T: int, L: int, device) -> torch.Tensor:
@@ -384,23 +483,25 @@ def window_pose_tick_workspace(T: int, L: int, device) -> torch.Tensor:
     return torch.empty(max(n, 1), dtype=torch.uint8, device=device)
 
 
-def window_pose_tick_pre(args, ws: torch.Tensor, *, lam: float) -> None:
+def window_pose_tick_pre(args, ws: torch.Tensor, *, lam: float, prior=None) -> None:
     """pa_window_pose_tick_pre on the device's current stream: the window advances without the
     new keypoints, every factor but the newest frame's projections, the GN system reduced to
     the newest frame (into ws)."""
     dev = ws.device
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().pa_window_pose_tick_pre(C.byref(args), float(lam), ws.data_ptr(), ws.numel(),
-                                                      _lib.stream_of(dev)), "pa_window_pose_tick_pre")
+        _lib.check(_lib.lib().pa_window_pose_tick_pre_prior(C.byref(args), float(lam), ws.data_ptr(), ws.numel(),
+                                                            *_prior_ptrs(prior), _lib.stream_of(dev)),
+                   "pa_window_pose_tick_pre")
 
 
-def window_pose_tick_reduce(args, ws: torch.Tensor, *, lam: float) -> None:
+def window_pose_tick_reduce(args, ws: torch.Tensor, *, lam: float, prior=None) -> None:
     """pa_window_pose_tick_reduce on the device's current stream: the pre half's reduction alone,
     from the factor outputs as they stand (no advance, no linearize)."""
     dev = ws.device
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().pa_window_pose_tick_reduce(C.byref(args), float(lam), ws.data_ptr(), ws.numel(),
-                                                         _lib.stream_of(dev)), "pa_window_pose_tick_reduce")
+        _lib.check(_lib.lib().pa_window_pose_tick_reduce_prior(C.byref(args), float(lam), ws.data_ptr(), ws.numel(),
+                                                               *_prior_ptrs(prior), _lib.stream_of(dev)),
+                   "pa_window_pose_tick_reduce")
 
 
 def window_pose_tick_post(args, y_new: torch.Tensor, ws: torch.Tensor, *, delta: torch.Tensor, info: torch.Tensor,

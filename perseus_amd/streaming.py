@@ -59,7 +59,16 @@ class StreamingPipeline:
     initial window (default: the cube 0.4 m in front of each camera, at rest);
     proj_robust = None, ("huber", k) or ("cauchy", k): GTSAM's noiseModel.Robust on the keypoint
     factors (pipeline.prepare_trajectories), so that a keypoint tens of pixels off, an occluded
-    corner, is down-weighted in every tick form, solve_window() and window_covariance()."""
+    corner, is down-weighted in every tick form, solve_window() and window_covariance().
+    marginalize=True: the fixed-lag smoother proper (GTSAM's BatchFixedLagSmoother): the frame a
+    tick drops is not forgotten but marginalized, its factors' Schur complement carried as a
+    linear prior on the oldest frame (pipeline.PriorPlan, self.prior).  Each tick then runs, inside
+    the same graph: the last tick's new prior becomes the current one (one device copy),
+    pa_window_prior_linearize at frame 1 of the un-advanced window (the frame about to become
+    the oldest), the tick in whatever form it uses with the prior on frame 0, and
+    pa_window_marginalize with the tick's delta and info.  self.prior.minfo (device, int32) is 2
+    until the window has filled, then 0.  Not with pre_ahead (between ticks the factor outputs
+    already belong to the next tick): ValueError; solve_window() raises with it on."""
 
     def __init__(self, model, n_cams: int = 3, src_hw=(720, 1280), bgr: bool = True, host_crop: bool = True,
                  graph: bool = True, near: float | None = None, far: float | None = None, device=None,
@@ -67,9 +76,16 @@ class StreamingPipeline:
                  proj_sigma: float = 1.0, dyn_sigma: float = 0.1, cv_sigma: float = 0.1, lam: float = 1e-2,
                  init_pose=None, init_vel=None, init_angvel=None, split_k: bool = True,
                  zero_copy: bool | None = None, split_pose: bool = True, pre_ahead: bool = False,
-                 zero_copy_out: bool = True, proj_robust=None):
+                 zero_copy_out: bool = True, proj_robust=None, marginalize: bool = False):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingPipeline needs a ROCm GPU (no CPU fallback)")
+        if marginalize and pre_ahead:
+            raise ValueError("StreamingPipeline: marginalize=True cannot run with pre_ahead=True (between ticks the "
+                             "factor outputs already belong to the next tick)")
+        if marginalize and not pose_window:
+            raise ValueError("StreamingPipeline: marginalize=True needs the pose stage (pose_window > 0)")
+        self.marginalize = bool(marginalize)
+        self.prior = None
         cam_K = K  # (the name K is the keypoint count below)
         # a 3-channel model takes the RGB half of each frame (scripts/streaming.py:104,126 with an
         # RGB model feeds frame[:C]: the depth is dropped): RGB-only staging, pa_detector_forward_rgb_px
@@ -228,8 +244,24 @@ class StreamingPipeline:
         elif self.pose_L and not self.split_pose:  # the fused / four-launch stages write the device block
             self.out_h[self._px_bytes:].copy_(self.out_d[self._px_bytes:], non_blocking=True)
 
+    def _enqueue_prior_in(self):
+        """marginalize: the last tick's new prior becomes the current one, and its gradient at
+        frame 1 of the un-advanced window, the frame the tick's advance makes the oldest."""
+        if self.prior is not None:
+            self.prior.advance()
+            self.prior.linearize(self.win["pose"], self.win["angvel"], self.win["vel"], frame=1)
+
+    def _enqueue_prior_out(self, info):
+        """marginalize: frame 0 of the tick's linearization becomes the next prior, re-centred at
+        the retracted window."""
+        if self.prior is not None:
+            self.prior.marginalize(self.lin, self.win["pose"], self.win["angvel"], self.win["vel"], lam=self.gn.lam,
+                                   delta=self.gn.out["delta"], gn_info=info, nvalid=self.nvalid,
+                                   n_kp=self.model.n_keypoints)
+
     def _enqueue_pose_pre(self):
-        pipeline.window_pose_tick_pre(self.traj_args, self.tick_ws, lam=self.gn.lam)
+        self._enqueue_prior_in()
+        pipeline.window_pose_tick_pre(self.traj_args, self.tick_ws, lam=self.gn.lam, prior=self.prior)
 
     def _enqueue_pose_post(self):
         if self._zc_out:  # info and the newest poses straight into the pinned output block
@@ -238,6 +270,7 @@ class StreamingPipeline:
             info, newest = self.gn.out["info"], self.pose_d
         pipeline.window_pose_tick_post(self.traj_args, self.y, self.tick_ws, delta=self.gn.out["delta"], info=info,
                                        newest=newest)
+        self._enqueue_prior_out(info)
 
     def _enqueue_pose(self):
         """The pose stage on the current stream, from the keypoints in self.y (HBM-resident window):
@@ -249,14 +282,16 @@ class StreamingPipeline:
                 self._enqueue_pose_pre()
             self._enqueue_pose_post()
             return
+        self._enqueue_prior_in()
         if self.fused_pose:
             pipeline.window_pose_tick(self.traj_args, self.y, lam=self.gn.lam, delta=self.gn.out["delta"],
-                                      info=self.gn.out["info"], newest=self.pose_d)
-            return
-        pipeline.window_advance(self.y, self.win, dt=self.dt, vel_frame=self.vel_frame, nvalid=self.nvalid)
-        pipeline.launch(self.traj_args, self.dev)
-        self.gn.launch()  # delta, and info straight into the output block
-        pipeline.window_retract(self.win, self.gn.out["delta"], self.gn.out["info"], newest=self.pose_d)
+                                      info=self.gn.out["info"], newest=self.pose_d, prior=self.prior)
+        else:
+            pipeline.window_advance(self.y, self.win, dt=self.dt, vel_frame=self.vel_frame, nvalid=self.nvalid)
+            pipeline.launch(self.traj_args, self.dev)
+            self.gn.launch()  # delta, and info straight into the output block
+            pipeline.window_retract(self.win, self.gn.out["delta"], self.gn.out["info"], newest=self.pose_d)
+        self._enqueue_prior_out(self.gn.out["info"])
 
     def _init_pose_stage(self, K, corners, dt, vel_frame, proj_sigma, dyn_sigma, cv_sigma, lam, init_pose, init_vel,
                          init_angvel, proj_robust=None):
@@ -288,7 +323,11 @@ class StreamingPipeline:
             nvalid=self.nvalid, proj_robust=proj_robust)
         for k in ("y", "pose", "vel", "angvel"):  # linearize reads the window in place, no staging copy
             assert self.lin["_keep"][("y", "pose", "vel", "angvel").index(k)].data_ptr() == self.win[k].data_ptr()
-        self.gn = pipeline.GNPlan(self.lin, T=n, L=Lw, lam=lam)
+        if self.marginalize:
+            # the prior on frame 0: the fused / split ticks get it beside the pa_traj_args (the _prior
+            # entry points), the four-launch path's GN step from the plan
+            self.prior = pipeline.PriorPlan(T=n, L=Lw, device=dev)
+        self.gn = pipeline.GNPlan(self.lin, T=n, L=Lw, lam=lam, prior=self.prior)
         self.gn.out["info"] = self.info_d  # the GN step writes info into the output block
         # pa_window_pose_tick: one workgroup per camera of up to 24 frames, at most one per CU
         self.fused_pose = (Lw <= pipeline.TICK_MAX_L
@@ -319,6 +358,8 @@ class StreamingPipeline:
         with torch.cuda.stream(self.stream):
             self.win["y"].zero_()
             self.nvalid.zero_()
+            if self.prior is not None:
+                self.prior.zero()
             for k in ("pose", "vel", "angvel"):
                 self.win[k].copy_(torch.as_tensor(self._init[k], device=self.dev)[:, None, :]
                                   .expand_as(self.win[k]))
@@ -347,6 +388,9 @@ class StreamingPipeline:
         if self.pose_L > pipeline.TICK_MAX_L:
             raise ValueError(f"solve_window(): pose_window {self.pose_L} > {pipeline.TICK_MAX_L}, the range of the "
                              "device Levenberg-Marquardt solve (pa_trajectory_lm_solve)")
+        if self.marginalize:
+            raise ValueError("solve_window(): the Levenberg-Marquardt solve has no marginalization prior (its cost "
+                             "would need the prior's err and a re-linearization per iteration); marginalize=True")
         key = (int(max_iters), tuple(sorted(params.items())))
         if getattr(self, "_lm_key", None) != key:
             self._lm = pipeline.LMPlan(self.traj_args, self.lin, T=self.n, L=self.pose_L, max_iters=max_iters,
@@ -372,14 +416,15 @@ class StreamingPipeline:
         (n,) int32 (0 = computed), as numpy.  Reads the factor outputs (self.lin) as they stand:
         the last tick's linearization (pre_ahead: the next tick's pre half's, so between ticks
         frame L-1 is the predicted one, its projection factors are out (status 3) and its
-        covariance is the prediction's, as window_state()).  lam defaults to the tick's; a window
+        covariance is the prediction's, as window_state()).  marginalize=True: with the prior the
+        last tick's step had on frame 0.  lam defaults to the tick's; a window
         that has not filled yet needs a lam of that order.  Runs eagerly on the pipeline's
         stream, outside the captured tick graph."""
         if not self.pose_L:
             raise RuntimeError("window_covariance() needs the pose stage (pose_window > 0)")
         lam = self.gn.lam if lam is None else float(lam)
         if getattr(self, "_marg", None) is None:
-            self._marg = pipeline.MarginalsPlan(self.lin, T=self.n, L=self.pose_L, lam=lam)
+            self._marg = pipeline.MarginalsPlan(self.lin, T=self.n, L=self.pose_L, lam=lam, prior=self.prior)
         self._marg.lam = lam
         with torch.cuda.stream(self.stream):
             self._marg.launch()
