@@ -340,7 +340,7 @@ int pa_trajectory_marginals(int T, int L, int n_kp, const double* r_proj, const 
  *      arithmetic), C' = the cost at x'; x' is rejected if a projection factor with status 0 at x
  *      has status 1 (cheirality) at x'; otherwise it is accepted iff C' < C.
  *   3. accept: x = x', lambda = max(lambda / lambda_down, lambda_min), status CONVERGED and stop
- *      if C - C' <= rel_tol * C + abs_tol; then C = C'.
+ *      if C - C' <= rel_tol * |C| + abs_tol (C >= 0 without a prior); then C = C'.
  *   4. reject: lambda *= lambda_up, status STALLED and stop if that exceeds lambda_max; x stays.
  *   5. cost_hist[k] = C after the decision; entries after the stop are NaN.
  * A trajectory still running after iteration max_iters stops with MAX_ITERS.
@@ -493,8 +493,12 @@ int pa_window_marginalize(int T, int L, int n_kp, const double* r_proj, const do
  * frame 0: the parent plus prior_info (T, 12, 12) and prior_grad (T, 12), given together; both NULL
  * is the parent, bit for bit.  (pa_traj_args itself is unchanged: the prior travels beside it.
  * pa_window_pose_tick_post needs no sibling, the prior is in the system the pre half reduced.)
- * pa_trajectory_lm_solve and pa_window_lm_solve have no such sibling and so take no prior: their
- * cost would need the prior's err and a re-linearization per iteration. */
+ * pa_trajectory_lm_solve and pa_window_lm_solve have their siblings too, pa_trajectory_lm_prior_solve
+ * and pa_window_lm_prior_solve below: their cost needs the prior's err and a re-linearization per
+ * iteration, so they take the whole prior (pa_lm_prior), not its gradient.  (Named ..._lm_prior_solve,
+ * after pa_trajectory_lm_prior_workspace, not ..._lm_solve_prior: the two-pointer convention of the
+ * _prior siblings here does not fit them, and tests/test_prior_capi.py pins that no entry point
+ * of that name takes it.) */
 int pa_trajectory_gn_step_prior(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
                                 const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
                                 const double* j_dyn1, const double* j_dyn2, const double* j_dyn3,
@@ -515,6 +519,48 @@ int pa_window_pose_tick_pre_prior(const pa_traj_args* args, double lambda, void*
                                   const double* prior_info, const double* prior_grad, void* stream);
 int pa_window_pose_tick_reduce_prior(const pa_traj_args* args, double lambda, void* ws_dev, size_t ws_bytes,
                                      const double* prior_info, const double* prior_grad, void* stream);
+
+
+/* Levenberg-Marquardt with the marginalization prior on frame 0: what GTSAM's BatchFixedLagSmoother
+ * runs on the host, an LM solve over the window's factors plus the marginal prior.  The parents'
+ * steps 1-5 (pa_trajectory_lm_solve above) with three additions:
+ *   cost  C = (the parent's sum, in its fixed order) + e_prior,
+ *         e_prior = sum_i xi_i (0.5 (Lambda xi)_i - eta_i), xi taken at frame 0 of the state being
+ *         evaluated, in exactly pa_window_prior_linearize's operation order (the same device code);
+ *         e_prior is added last, unfused.
+ *   step  (J^T J + lambda I + Lambda on frame 0) delta = -(J^T r + (Lambda xi - eta) on frame 0), xi at
+ *         the CURRENT state x (pa_trajectory_gn_step_prior's system): the gradient is re-evaluated
+ *         with every trial state and kept with an accepted one.
+ *   sign  -eta^T xi has no lower bound, so C can be negative: the convergence test of step 3 is
+ *         C - C' <= rel_tol * |C| + abs_tol (for the parents C >= 0: the same bits).  The accept test
+ *         stays C' < C.
+ * prior == NULL is the parent, bit for bit, and accepts the parent's workspace size; the parents
+ * are calls of these with NULL.  A non-null prior needs info, eta, xbar_* and grad (PA_EINVAL
+ * before any launch otherwise) and pa_trajectory_lm_prior_workspace bytes (>= the parent's; 0
+ * outside the limits).  On return grad / err hold the prior's gradient and cost at frame 0 of the
+ * final accepted state, bit for bit what pa_window_prior_linearize(frame 0) gives there: grad is
+ * the prior_grad_in that pa_window_marginalize takes with the factor outputs the solve leaves.
+ * Limits, nvalid, robust_proj, newest_pending, launch count (1 + 2 max_iters, capturable): the
+ * parents'. */
+typedef struct pa_lm_prior {
+  const double* info;        /* (T,12,12) Lambda, row-major, symmetric              */
+  const double* eta;         /* (T,12)                                              */
+  const double* xbar_pose;   /* (T,12)  the state the prior was linearized at       */
+  const double* xbar_angvel; /* (T,3)                                               */
+  const double* xbar_vel;    /* (T,3)                                               */
+  double* grad;              /* (T,12) OUT, required: Lambda xi - eta at the final accepted state */
+  double* err;               /* (T)    OUT or NULL: 0.5 xi'Lambda xi - eta'xi there */
+} pa_lm_prior;
+
+size_t pa_trajectory_lm_prior_workspace(int T, int L, int n_kp, int max_iters);
+int pa_trajectory_lm_prior_solve(const pa_traj_args* args, const pa_lm_params* p, const pa_lm_prior* prior,
+                                 double* cost0_dev, double* cost_dev, int32_t* iters_dev, int32_t* status_dev,
+                                 double* lambda_dev, double* cost_hist_dev, void* ws_dev, size_t ws_bytes,
+                                 void* stream);
+int pa_window_lm_prior_solve(const pa_traj_args* args, const pa_lm_params* p, int newest_pending,
+                             const pa_lm_prior* prior, double* cost0_dev, double* cost_dev, int32_t* iters_dev,
+                             int32_t* status_dev, double* lambda_dev, double* cost_hist_dev, void* ws_dev,
+                             size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,13 @@ class LMParams(C.Structure):
                 ("rel_tol", C.c_double), ("abs_tol", C.c_double)]
 
 
+class LMPrior(C.Structure):
+    """Mirror of `pa_lm_prior` (include/perseus_amd.h)."""
+
+    _fields_ = [("info", C.c_void_p), ("eta", C.c_void_p), ("xbar_pose", C.c_void_p), ("xbar_angvel", C.c_void_p),
+                ("xbar_vel", C.c_void_p), ("grad", C.c_void_p), ("err", C.c_void_p)]
+
+
 class DebugTap(C.Structure):
     """Mirror of `pa_debug_tap` (include/perseus_amd_debug.h)."""
 
@@ -69,6 +76,11 @@ _SIGS = {
                                + [C.c_size_t, C.c_void_p]),
     "pa_window_lm_solve": (C.c_int, [C.POINTER(TrajArgs), C.POINTER(LMParams), C.c_int] + [C.c_void_p] * 7
                            + [C.c_size_t, C.c_void_p]),
+    "pa_trajectory_lm_prior_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pa_trajectory_lm_prior_solve": (C.c_int, [C.POINTER(TrajArgs), C.POINTER(LMParams), C.POINTER(LMPrior)]
+                                     + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "pa_window_lm_prior_solve": (C.c_int, [C.POINTER(TrajArgs), C.POINTER(LMParams), C.c_int, C.POINTER(LMPrior)]
+                                 + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
     "pa_window_pose_tick_reduce": (C.c_int, [C.POINTER(TrajArgs), C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pa_trajectory_linearize": (C.c_int, [C.POINTER(TrajArgs), C.c_void_p]),
     "pa_debug_trajectory_linearize": (C.c_int, [C.POINTER(TrajArgs), C.c_int, C.c_void_p, C.c_void_p]),
@@ -213,10 +225,20 @@ def lib(build_if_missing: bool = True):
     if not os.path.exists(path):
         raise PerseusError(f"{path} not found: run `python -m perseus_amd.build`")
     L = C.CDLL(path)
+    missing = []
     for name, (res, args) in _SIGS.items():
+        if path != _build.LIB and not hasattr(L, name):
+            # an older build under A/B lacks the newer entry points (the in-tree library must have all)
+            missing.append(name)
+            continue
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args
+    if missing:
+        import warnings
+
+        warnings.warn(f"{path} (PERSEUS_AMD_LIB_AB) lacks {', '.join(missing)}: calling them raises AttributeError",
+                      RuntimeWarning, stacklevel=2)
     _LIB = L
     return L
 

@@ -1,6 +1,8 @@
-// pa_trajectory_lm_solve / pa_window_lm_solve: Levenberg-Marquardt per trajectory on the device,
-// around the damped step of gn_cr_run (gn_cr_dev.h) and the factors of factors_dev.h.
+// pa_trajectory_lm_solve / pa_window_lm_solve and their ..._lm_prior_solve siblings (the
+// marginalization prior on frame 0 in the cost and the steps): Levenberg-Marquardt per trajectory
+// on the device, around the damped step of gn_cr_run (gn_cr_dev.h) and the factors of factors_dev.h.
 #include "gn_cr_dev.h"
+#include "prior_dev.h"
 
 namespace pa {
 
@@ -22,6 +24,24 @@ namespace pa {
 // A trajectory that stops leaves its final linearization in the caller's outputs (copied from
 // set 1 if that was current) and its workgroups return at once in every later launch.  No
 // workgroup reads what another writes within a launch.
+//
+// With a marginalization prior on frame 0 (pa_trajectory_lm_prior_solve; prior.hip):
+//   cost    C = (the sum above) + e_prior, e_prior = sum_i xi_i (0.5 (Lambda xi)_i - eta_i) with xi at
+//           frame 0 of the state being evaluated, by prior_lin_wave (pa_window_prior_linearize's
+//           instructions), added last on the deciding lane with contraction off.  lm_lin_kernel's
+//           last wave, which traj_lin_block leaves idle, evaluates it before the first barrier.
+//   step    (J^T J + lambda_t I + Lambda on frame 0) delta = -(J^T r + (Lambda xi - eta) on frame 0):
+//           GnArgs.p_info / p_grad.  The gradient belongs to a linearization, so it lives per
+//           factor set (set 0: the caller's prior->grad, set 1: the workspace's), is written with
+//           the target set's factors and goes to the caller with them when a trajectory stops
+//           with set 1 current.
+//   sign    -eta^T xi has no lower bound, so C may be negative: the convergence test is
+//           C - C' <= rel_tol |C| + abs_tol (the same bits where C >= 0).
+struct LmPriorDev {
+  const double *info, *eta, *xp, *xw, *xv;  // the caller's prior; info == nullptr: none
+  double *g0, *g1;                          // (T, 12) the gradient of set 0 (the caller's), set 1 (the workspace's)
+  double *err, *err_out;                    // (T) e_prior at the current state (workspace), the caller's or nullptr
+};
 struct LmDev {
   FactorSet s0, s1;              // the caller's factor outputs, the workspace's
   double *pose, *vel, *angvel;   // the trial state (T*L, 12 / 3 / 3)
@@ -33,6 +53,7 @@ struct LmDev {
   int32_t *iters, *status;
   pa_lm_params p;
   int pending;  // the newest frame's keypoints are not in yet (pa_window_lm_solve): its projections get status 3
+  LmPriorDev pr;
 };
 
 __device__ __forceinline__ FactorSet lm_pick(const LmDev& d, int which) {  // (uniform selects, no indexed copy)
@@ -55,8 +76,9 @@ __device__ __forceinline__ void lm_copy(V* dst, const V* src, long n) {
 
 // launch k = 0: the initial state (ta.pose / vel / angvel) into set 0; k >= 1: the trial state of
 // iteration k into the set that is not current, then the decision.  RB: ta.robust_proj names a
-// robust noise model (the cost is then the sum of its rho; the decision logic is the same)
-template <bool RB>
+// robust noise model (the cost is then the sum of its rho; the decision logic is the same).
+// PR: d.pr holds a prior on frame 0
+template <bool RB, bool PR>
 __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta, LmDev d, int k) {
   __shared__ __attribute__((aligned(16))) double st[LIN_STAGE];
   __shared__ int dec_s;
@@ -66,6 +88,7 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta
   const int cur = k > 0 ? d.cur[t] : 0;
   const int tgt = k > 0 ? 1 - cur : 0;
   const bool pivot = k > 0 && d.info[t] != 0;  // the step's solve failed: a reject, nothing to evaluate
+  [[maybe_unused]] const double* pe_p = nullptr;
   const FactorSet so = lm_pick(d, tgt), sc = lm_pick(d, cur);
   const long f0 = (long)t * L, p0 = f0 * K, d0 = (long)t * (L - 1);
   double* xp = const_cast<double*>(ta.pose) + f0 * 12;
@@ -77,6 +100,18 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta
     a1.vel = k > 0 ? d.vel + f0 * 3 : xv;
     a1.angvel = k > 0 ? d.angvel + f0 * 3 : xw;
     traj_lin_block<RB>(a1, st);
+    if constexpr (PR) {
+      // the prior at frame 0 of the state just linearized: grad to the target set, e_prior to wave 0
+      __shared__ double pxi[gn::NV], pes[gn::NV], pe_s;
+      if (wv == TICK_LIN_W - 1) {
+        const LmPriorDev& q = d.pr;
+        const double e = prior_lin_wave(lane, q.info + (size_t)t * gn::NB, q.eta + (size_t)t * gn::NV,
+                                        q.xp + (size_t)t * 12, q.xw + (size_t)t * 3, q.xv + (size_t)t * 3, a1.pose,
+                                        a1.angvel, a1.vel, (tgt ? q.g1 : q.g0) + (size_t)t * gn::NV, pxi, pes);
+        if (lane == 0) pe_s = e;
+      }
+      pe_p = &pe_s;
+    }
   }
   if (k == 0)
     for (int e = 1 + (int)threadIdx.x; e < M1; e += 64 * TICK_LIN_W) d.hist[(size_t)t * M1 + e] = NAN;
@@ -117,6 +152,13 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta
       const pa_lm_params& p = d.p;
       double C, lam;
       int status = 0, acc = 0, ncur = cur;
+      [[maybe_unused]] double pe = 0.0;
+      if constexpr (PR) {
+        if (!pivot) {
+          pe = *pe_p;
+          s = s + pe;
+        }
+      }
       if (k == 0) {
         C = s;
         lam = p.lambda0;
@@ -128,7 +170,7 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta
           acc = 1;
           ncur = tgt;
           lam = fmax(lam / p.lambda_down, p.lambda_min);
-          const double tol = p.rel_tol * C;
+          const double tol = p.rel_tol * fabs(C);
           if (C - s <= tol + p.abs_tol) status = PA_LM_CONVERGED;
           C = s;
         } else {
@@ -146,6 +188,11 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta
       d.lam_out[t] = lam;
       d.iters[t] = k;
       d.status[t] = status;
+      if constexpr (PR) {  // e_prior at the current state: the evaluated one's on launch 0 and on an accept
+        const double ce = (k == 0 || acc) ? pe : d.pr.err[t];
+        d.pr.err[t] = ce;
+        if (d.pr.err_out) d.pr.err_out[t] = ce;
+      }
       dec_s = acc | (status != 0 ? 2 : 0) | (ncur << 2);
     }
   }
@@ -162,11 +209,14 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta
   lm_copy(d.s0.f + factor_units(u, p0, d0) * n, d.s1.f + factor_units(u, p0, d0) * n, factor_units(u, np, nd) * n);
     PA_FACTOR_OUTPUTS(PA_X)
 #undef PA_X
+    if constexpr (PR) lm_copy(d.pr.g0 + (size_t)t * gn::NV, d.pr.g1 + (size_t)t * gn::NV, (long)gn::NV);
   }
 }
 
-// iteration k's damped step from the current set, then the trial state into d.pose / vel / angvel
-template <int RP>
+// iteration k's damped step from the current set, then the trial state into d.pose / vel / angvel.
+// PR: with d.pr's Lambda and the current set's prior gradient on frame 0 (the instantiations
+// without it are the code they were before the prior existed)
+template <int RP, bool PR>
 __global__ __launch_bounds__(64 * GN_CR_W, 1) void lm_step_kernel(int T, int L, int K, LmDev d,
                                                                    const double* __restrict__ pose,
                                                                    const double* __restrict__ vel,
@@ -177,7 +227,12 @@ __global__ __launch_bounds__(64 * GN_CR_W, 1) void lm_step_kernel(int T, int L, 
   __shared__ __attribute__((aligned(16))) double pool[Ld::POOL];
   const int t = blockIdx.x;
   if (d.done[t] != 0) return;  // (uniform)
-  const GnArgs g = gn_args(T, L, K, lm_pick(d, d.cur[t]), d.lam[t], d.delta, d.info, nullptr);
+  const int cur = d.cur[t];
+  GnArgs g = gn_args(T, L, K, lm_pick(d, cur), d.lam[t], d.delta, d.info, nullptr);
+  if constexpr (PR) {
+    g.p_info = d.pr.info;
+    g.p_grad = cur ? d.pr.g1 : d.pr.g0;
+  }
   gn_cr_run<RP, NS>(g, t, fb, pool);
   __syncthreads();
   if ((int)threadIdx.x < L) {
@@ -194,14 +249,15 @@ __global__ __launch_bounds__(64 * GN_CR_W, 1) void lm_step_kernel(int T, int L, 
 }
 
 // the workspace: set 1 of the factor outputs, the trial state, delta, the per-trajectory LM
-// state and a cost history (used when the caller passes none); every array 16-B aligned
+// state and a cost history (used when the caller passes none); with a prior, after all of that,
+// set 1's prior gradient (T, 12) and the current e_prior (T); every array 16-B aligned
 struct LmLayout {
 #define PA_X(f, V, n, u) size_t f;
   PA_FACTOR_OUTPUTS(PA_X)
 #undef PA_X
-  size_t pose, vel, angvel, delta, C, lam, done, cur, info, hist, bytes;
+  size_t pose, vel, angvel, delta, C, lam, done, cur, info, hist, pgrad, perr, bytes;
 };
-static LmLayout lm_layout(int T, int L, int K, int max_iters) {
+static LmLayout lm_layout(int T, int L, int K, int max_iters, bool prior) {
   LmLayout o;
   size_t at = 0;
   auto take = [&](size_t n, size_t el) {
@@ -223,6 +279,11 @@ static LmLayout lm_layout(int T, int L, int K, int max_iters) {
   o.cur = take(T, 4);
   o.info = take(T, 4);
   o.hist = take((size_t)T * ((size_t)max_iters + 1), 8);
+  o.pgrad = o.perr = at;
+  if (prior) {
+    o.pgrad = take((size_t)T * 12, 8);
+    o.perr = take(T, 8);
+  }
   o.bytes = at;
   return o;
 }
@@ -233,13 +294,21 @@ extern "C" {
 
 size_t pa_trajectory_lm_workspace(int T, int L, int n_kp, int max_iters) {
   if (T < 1 || L < 2 || L > pa::GN_CR_LMAX || n_kp < 1 || n_kp > pa::GN_KMAX || max_iters < 1) return 0;
-  return pa::lm_layout(T, L, n_kp, max_iters).bytes;
+  return pa::lm_layout(T, L, n_kp, max_iters, false).bytes;
 }
 
-static int lm_solve_impl(const pa_traj_args* ta, const pa_lm_params* p, int pending, double* cost0, double* cost,
-                         int32_t* iters, int32_t* status, double* lambda, double* cost_hist, void* ws,
-                         size_t ws_bytes, void* stream) {
+size_t pa_trajectory_lm_prior_workspace(int T, int L, int n_kp, int max_iters) {
+  if (T < 1 || L < 2 || L > pa::GN_CR_LMAX || n_kp < 1 || n_kp > pa::GN_KMAX || max_iters < 1) return 0;
+  return pa::lm_layout(T, L, n_kp, max_iters, true).bytes;
+}
+
+static int lm_solve_impl(const pa_traj_args* ta, const pa_lm_params* p, int pending, const pa_lm_prior* prior,
+                         double* cost0, double* cost, int32_t* iters, int32_t* status, double* lambda,
+                         double* cost_hist, void* ws, size_t ws_bytes, void* stream) {
   PA_CHECK(ta && p, "lm: null args / params");
+  PA_CHECK(!prior || (prior->info && prior->eta && prior->xbar_pose && prior->xbar_angvel && prior->xbar_vel),
+           "lm: null info / eta / xbar_pose / xbar_angvel / xbar_vel in a non-null prior");
+  PA_CHECK(!prior || prior->grad, "lm: null grad in a non-null prior (the final gradient is a required output)");
   if (const int rc = pa::robust_check(*ta, "lm")) return rc;
   const int T = ta->T, L = ta->L, K = ta->n_kp;
   PA_CHECK(T >= 0 && L >= 2 && L <= pa::GN_CR_LMAX && K >= 1 && K <= pa::GN_KMAX,
@@ -260,7 +329,7 @@ static int lm_solve_impl(const pa_traj_args* ta, const pa_lm_params* p, int pend
   PA_FACTOR_OUTPUTS(PA_X)
 #undef PA_X
   PA_CHECK(cost0 && cost && iters && status && lambda, "lm: null cost0 / cost / iters / status / lambda output");
-  const pa::LmLayout o = pa::lm_layout(T, L, K, p->max_iters);
+  const pa::LmLayout o = pa::lm_layout(T, L, K, p->max_iters, prior != nullptr);
   PA_CHECK(ws && ws_bytes >= o.bytes, "lm: workspace %zu < %zu", ws ? ws_bytes : (size_t)0, o.bytes);
   PA_CHECK(((uintptr_t)ws & 15) == 0, "lm: workspace not 16-byte aligned");
   char* w = (char*)ws;
@@ -288,13 +357,21 @@ static int lm_solve_impl(const pa_traj_args* ta, const pa_lm_params* p, int pend
   d.status = status;
   d.p = *p;
   d.pending = pending;
+  d.pr = pa::LmPriorDev{};
+  if (prior)
+    d.pr = pa::LmPriorDev{prior->info, prior->eta, prior->xbar_pose, prior->xbar_angvel, prior->xbar_vel,
+                          prior->grad, f64(o.pgrad), f64(o.perr), prior->err};
   const hipStream_t s = (hipStream_t)stream;
-  const auto lin_kernel = ta->robust_proj == PA_ROBUST_NONE ? pa::lm_lin_kernel<false> : pa::lm_lin_kernel<true>;
+  const bool rb = ta->robust_proj != PA_ROBUST_NONE;
+  const auto lin_kernel = prior ? (rb ? pa::lm_lin_kernel<true, true> : pa::lm_lin_kernel<false, true>)
+                                : (rb ? pa::lm_lin_kernel<true, false> : pa::lm_lin_kernel<false, false>);
   for (int k = 0; k <= p->max_iters; ++k) {
     if (k > 0)
       pa::gn_for_kp(K, [&](auto rp) {
-        hipLaunchKernelGGL(pa::lm_step_kernel<decltype(rp)::value>, dim3(T), dim3(64 * pa::GN_CR_W), 0, s, T, L, K, d,
-                           ta->pose, ta->vel, ta->angvel);
+        constexpr int RP = decltype(rp)::value;
+        const auto step_kernel = prior ? pa::lm_step_kernel<RP, true> : pa::lm_step_kernel<RP, false>;
+        hipLaunchKernelGGL(step_kernel, dim3(T), dim3(64 * pa::GN_CR_W), 0, s, T, L, K, d, ta->pose, ta->vel,
+                           ta->angvel);
       });
     hipLaunchKernelGGL(lin_kernel, dim3(T), dim3(64 * pa::TICK_LIN_W), 0, s, *ta, d, k);
   }
@@ -302,16 +379,31 @@ static int lm_solve_impl(const pa_traj_args* ta, const pa_lm_params* p, int pend
   return PA_OK;
 }
 
+int pa_trajectory_lm_prior_solve(const pa_traj_args* ta, const pa_lm_params* p, const pa_lm_prior* prior,
+                                 double* cost0, double* cost, int32_t* iters, int32_t* status, double* lambda,
+                                 double* cost_hist, void* ws, size_t ws_bytes, void* stream) {
+  return lm_solve_impl(ta, p, 0, prior, cost0, cost, iters, status, lambda, cost_hist, ws, ws_bytes, stream);
+}
+
+int pa_window_lm_prior_solve(const pa_traj_args* ta, const pa_lm_params* p, int newest_pending,
+                             const pa_lm_prior* prior, double* cost0, double* cost, int32_t* iters, int32_t* status,
+                             double* lambda, double* cost_hist, void* ws, size_t ws_bytes, void* stream) {
+  return lm_solve_impl(ta, p, newest_pending != 0, prior, cost0, cost, iters, status, lambda, cost_hist, ws, ws_bytes,
+                       stream);
+}
+
 int pa_trajectory_lm_solve(const pa_traj_args* ta, const pa_lm_params* p, double* cost0, double* cost, int32_t* iters,
                            int32_t* status, double* lambda, double* cost_hist, void* ws, size_t ws_bytes,
                            void* stream) {
-  return lm_solve_impl(ta, p, 0, cost0, cost, iters, status, lambda, cost_hist, ws, ws_bytes, stream);
+  return pa_trajectory_lm_prior_solve(ta, p, nullptr, cost0, cost, iters, status, lambda, cost_hist, ws, ws_bytes,
+                                      stream);
 }
 
 int pa_window_lm_solve(const pa_traj_args* ta, const pa_lm_params* p, int newest_pending, double* cost0, double* cost,
                        int32_t* iters, int32_t* status, double* lambda, double* cost_hist, void* ws, size_t ws_bytes,
                        void* stream) {
-  return lm_solve_impl(ta, p, newest_pending != 0, cost0, cost, iters, status, lambda, cost_hist, ws, ws_bytes, stream);
+  return pa_window_lm_prior_solve(ta, p, newest_pending, nullptr, cost0, cost, iters, status, lambda, cost_hist, ws,
+                                  ws_bytes, stream);
 }
 
 }  // extern "C"

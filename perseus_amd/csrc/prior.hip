@@ -26,7 +26,7 @@
 //             matrix cores, and the right-hand side in its column 12),
 // Lambda' symmetrized as (X + X^T) / 2 through LDS exactly as the marginals kernel does, and
 // re-centred to first order at the retracted state: g' += Lambda' delta_1.
-#include "gn_dev.h"
+#include "prior_dev.h"
 
 namespace pa {
 
@@ -48,35 +48,10 @@ __global__ __launch_bounds__(64) void prior_lin_kernel(int L, int frame, const d
   __shared__ double xi[NV], es[NV];
   const int t = blockIdx.x, i = threadIdx.x;
   const long f = (long)t * L + frame;
-  // every lane evaluates the same xi (uniform addresses: one Logmap's worth of instructions)
-  const Pose d = compose(inverse(load_pose(xp + (size_t)t * 12)), load_pose(pose + f * 12));
-  V3 w, u;
-  pose_log(d, w, u);
-  const V3 dw = load3(angvel + f * 3) - load3(xw + (size_t)t * 3);
-  const V3 dv = load3(vel + f * 3) - load3(xv + (size_t)t * 3);
-  if (i == 0) {
-    xi[0] = w.x, xi[1] = w.y, xi[2] = w.z;
-    xi[3] = u.x, xi[4] = u.y, xi[5] = u.z;
-    xi[6] = dw.x, xi[7] = dw.y, xi[8] = dw.z;
-    xi[9] = dv.x, xi[10] = dv.y, xi[11] = dv.z;
-  }
-  wave_order();
-  if (i < NV) {
-    const double* row = info + (size_t)t * NB + i * NV;
-    double lx = 0.0;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) lx = fma(row[k], xi[k], lx);
-    const double e = eta[(size_t)t * NV + i];
-    grad[(size_t)t * NV + i] = lx - e;
-    es[i] = xi[i] * (0.5 * lx - e);
-  }
-  wave_order();
-  if (err && i == 0) {
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) s += es[k];
-    err[t] = s;
-  }
+  const double s = prior_lin_wave(i, info + (size_t)t * NB, eta + (size_t)t * NV, xp + (size_t)t * 12,
+                                  xw + (size_t)t * 3, xv + (size_t)t * 3, pose + f * 12, angvel + f * 3, vel + f * 3,
+                                  grad + (size_t)t * NV, xi, es);
+  if (err && i == 0) err[t] = s;
 }
 
 template <int RP>

@@ -367,9 +367,13 @@ class LMPlan:
     int32 (_lib.LM_CONVERGED / LM_MAX_ITERS / LM_STALLED), cost_hist (T, max_iters + 1) f64 (NaN
     after a trajectory's stop).  Keywords: the fields of pa_lm_params (LM_DEFAULTS).
     newest_pending: the window is the one the split tick's pre half leaves between ticks (frame
-    L-1 predicted, its keypoints not in yet): its projection factors stay out (pa_window_lm_solve)."""
+    L-1 predicted, its keypoints not in yet): its projection factors stay out (pa_window_lm_solve).
+    prior (optional, a PriorPlan): the marginalization prior on frame 0 (pa_trajectory_lm_prior_solve /
+    pa_window_lm_prior_solve): its current Lambda, eta and xbar enter the cost and every step, and
+    after launch() prior.grad / prior.err hold its gradient and cost at the solved frame 0, the
+    prior_grad_in PriorPlan.marginalize consumes with `lin`."""
 
-    def __init__(self, args, lin: dict, *, T: int, L: int, newest_pending: bool = False, **params):
+    def __init__(self, args, lin: dict, *, T: int, L: int, newest_pending: bool = False, prior=None, **params):
         unknown = set(params) - set(LM_DEFAULTS)
         if unknown:
             raise TypeError(f"LMPlan: unknown parameters {sorted(unknown)}")
@@ -384,14 +388,24 @@ class LMPlan:
         self.args, self.lin, self.T, self.L, self.dev = args, lin, T, L, dev
         self.max_iters = int(p["max_iters"])
         self.newest_pending = bool(newest_pending)
+        self.prior = prior
+        if prior is not None and (prior.T, prior.L) != (T, L):
+            raise ValueError(f"LMPlan: the prior is for T {prior.T}, L {prior.L}, the solve for T {T}, L {L}")
 
         def e(*shape, dtype=torch.float64):
             return torch.empty(shape, dtype=dtype, device=dev)
 
         self.out = {"cost0": e(T), "cost": e(T), "lambda": e(T), "iters": e(T, dtype=torch.int32),
                     "status": e(T, dtype=torch.int32), "cost_hist": e(T, max(self.max_iters, 0) + 1)}
-        n = int(_lib.lib().pa_trajectory_lm_workspace(T, L, int(args.n_kp), self.max_iters))
+        size = _lib.lib().pa_trajectory_lm_workspace if prior is None else _lib.lib().pa_trajectory_lm_prior_workspace
+        n = int(size(T, L, int(args.n_kp), self.max_iters))
         self.ws = torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
+
+    def _prior_struct(self):
+        """The pa_lm_prior of self.prior as its buffers stand (they keep their addresses)."""
+        p, c = _lib.ptr, self.prior.cur
+        return _lib.LMPrior(p(c["info"]), p(c["eta"]), p(c["xbar_pose"]), p(c["xbar_angvel"]), p(c["xbar_vel"]),
+                            p(self.prior.grad), p(self.prior.err))
 
     def launch(self) -> None:
         """One pa_trajectory_lm_solve on the device's current stream."""
@@ -399,7 +413,16 @@ class LMPlan:
         with torch.cuda.device(self.dev):
             tail = (p(o["cost0"]), p(o["cost"]), p(o["iters"]), p(o["status"]), p(o["lambda"]), p(o["cost_hist"]),
                     p(self.ws), self.ws.numel(), _lib.stream_of(self.dev))
-            if self.newest_pending:
+            if self.prior is not None:
+                pr = self._prior_struct()
+                if self.newest_pending:
+                    _lib.check(_lib.lib().pa_window_lm_prior_solve(C.byref(self.args), C.byref(self.params), 1,
+                                                                   C.byref(pr), *tail), "pa_window_lm_prior_solve")
+                else:
+                    _lib.check(_lib.lib().pa_trajectory_lm_prior_solve(C.byref(self.args), C.byref(self.params),
+                                                                       C.byref(pr), *tail),
+                               "pa_trajectory_lm_prior_solve")
+            elif self.newest_pending:
                 _lib.check(_lib.lib().pa_window_lm_solve(C.byref(self.args), C.byref(self.params), 1, *tail),
                            "pa_window_lm_solve")
             else:
@@ -410,7 +433,7 @@ class LMPlan:
 def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: int, dt: float, proj_sigmas, dyn_sigmas,
              cv_sigmas, nvalid: torch.Tensor | None = None, vel_frame: str = "world", camera_pose=None, H: int = 256,
              W: int = 256, newest_pending: bool = False, covariance: bool = False, cov_lambda: float = 1e-9,
-             proj_robust=None, **params) -> dict:
+             proj_robust=None, prior=None, **params) -> dict:
     """Smoothed trajectories: Levenberg-Marquardt over all factors of T trajectories x L frames
     from the keypoints `y` (device) and the initial state, on the device (pa_trajectory_lm_solve;
     layouts as linearize_trajectories, the inputs are not modified).  Returns pose (T*L, 12),
@@ -422,20 +445,23 @@ def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: in
     (pipeline.marginals) of the linearization the solve leaves at the final state, with
     lam = cov_lambda (partly filled or pending windows need about 1e-2, see MarginalsPlan).
     proj_robust: as prepare_trajectories; the cost is then the sum of the m-estimator's losses and
-    the covariance that of the sqrt(w)-weighted system at the final state."""
+    the covariance that of the sqrt(w)-weighted system at the final state.
+    prior (a PriorPlan): the marginalization prior on frame 0 (LMPlan); its grad / err are updated, and
+    the covariance then has its Lambda in frame 0's block."""
     dev = y.device
     P, V, Wv = (_f64(a, dev).clone() for a in (poses, vels, angvels))  # updated in place: never the caller's
     a, lin = prepare_trajectories(y, P, V, Wv, corners, K, T=T, L=L, dt=dt, vel_frame=vel_frame,
                                   camera_pose=camera_pose, H=H, W=W, proj_sigmas=proj_sigmas, dyn_sigmas=dyn_sigmas,
                                   cv_sigmas=cv_sigmas, nvalid=nvalid, proj_robust=proj_robust)
     P, V, Wv = lin["_keep"][1:4]
-    plan = LMPlan(a, lin, T=T, L=L, newest_pending=newest_pending, **params)
+    plan = LMPlan(a, lin, T=T, L=L, newest_pending=newest_pending, prior=prior, **params)
     plan.launch()
     out = dict(plan.out)
     out.update(pose=P, vel=V, angvel=Wv, lin=lin, _ws=plan.ws)
     if covariance:
-        m = marginals(lin, T=T, L=L, lam=cov_lambda)
-        out.update(cov=m["cov"], cov_info=m["info"], _cov_ws=m["_ws"])
+        mp = MarginalsPlan(lin, T=T, L=L, lam=cov_lambda, prior=prior)
+        mp.launch()
+        out.update(cov=mp.out["cov"], cov_info=mp.out["info"], _cov_ws=mp.ws)
     return out
 
 

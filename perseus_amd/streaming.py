@@ -68,7 +68,8 @@ class StreamingPipeline:
     the oldest), the tick in whatever form it uses with the prior on frame 0, and
     pa_window_marginalize with the tick's delta and info.  self.prior.minfo (device, int32) is 2
     until the window has filled, then 0.  Not with pre_ahead (between ticks the factor outputs
-    already belong to the next tick): ValueError; solve_window() raises with it on."""
+    already belong to the next tick): ValueError.  solve_window(with_prior=True) is the
+    Levenberg-Marquardt solve of such a window with its prior; without the keyword it raises."""
 
     def __init__(self, model, n_cams: int = 3, src_hw=(720, 1280), bgr: bool = True, host_crop: bool = True,
                  graph: bool = True, near: float | None = None, far: float | None = None, device=None,
@@ -367,7 +368,7 @@ class StreamingPipeline:
                 self._enqueue_pose_pre()
         self.stream.synchronize()
 
-    def solve_window(self, max_iters: int = 20, **params) -> dict:
+    def solve_window(self, max_iters: int = 20, *, with_prior: bool = False, **params) -> dict:
         """Levenberg-Marquardt on the current window of every camera (pipeline.LMPlan,
         pa_trajectory_lm_solve): the tick takes ONE fixed-lambda step per frame, which nothing
         protects when the window is far from the truth (start-up from the guessed init_pose);
@@ -382,22 +383,38 @@ class StreamingPipeline:
         pre half's reduction is then redone on the solved window (pa_window_pose_tick_reduce:
         the whole pre half would advance the window a second time).
         Windows above 24 frames (pipeline.TICK_MAX_L, the cyclic-reduction solver's range) run
-        the four-launch tick but have no LM solve: ValueError."""
+        the four-launch tick but have no LM solve: ValueError.
+        marginalize=True: the window's factors alone are not the problem the ticks solve, so the
+        plain solve raises ValueError; with_prior=True runs the solve with the current prior on
+        frame 0 (pa_trajectory_lm_prior_solve: BatchFixedLagSmoother's optimize) and then
+        re-derives the NEXT prior from the linearization at the solved window (pa_window_marginalize
+        with the gradient the solve leaves, no damping step to re-centre by), as that smoother
+        marginalizes at its optimized point.  No buffer moves: the captured tick graph stays valid.
+        with_prior=True on a pipeline without marginalize=True: ValueError."""
         if not self.pose_L:
             raise RuntimeError("solve_window() needs the pose stage (pose_window > 0)")
         if self.pose_L > pipeline.TICK_MAX_L:
             raise ValueError(f"solve_window(): pose_window {self.pose_L} > {pipeline.TICK_MAX_L}, the range of the "
                              "device Levenberg-Marquardt solve (pa_trajectory_lm_solve)")
-        if self.marginalize:
-            raise ValueError("solve_window(): the Levenberg-Marquardt solve has no marginalization prior (its cost "
-                             "would need the prior's err and a re-linearization per iteration); marginalize=True")
+        if self.marginalize and not with_prior:
+            raise ValueError("solve_window(): marginalize=True, and the plain Levenberg-Marquardt solve would leave the "
+                             "marginalization prior out of its cost and steps; solve_window(with_prior=True) runs the "
+                             "solve with the prior on frame 0")
+        if with_prior and not self.marginalize:
+            raise ValueError("solve_window(with_prior=True) needs a pipeline built with marginalize=True (there is no "
+                             "prior to solve with)")
         key = (int(max_iters), tuple(sorted(params.items())))
         if getattr(self, "_lm_key", None) != key:
             self._lm = pipeline.LMPlan(self.traj_args, self.lin, T=self.n, L=self.pose_L, max_iters=max_iters,
-                                       newest_pending=self.pre_ahead, **params)
+                                       newest_pending=self.pre_ahead, prior=self.prior if with_prior else None,
+                                       **params)
             self._lm_key = key
         with torch.cuda.stream(self.stream):
             self._lm.launch()
+            if with_prior:  # the next prior from the linearization at the solved window
+                self.prior.marginalize(self.lin, self.win["pose"], self.win["angvel"], self.win["vel"],
+                                       lam=self.gn.lam, delta=None, gn_info=None, nvalid=self.nvalid,
+                                       n_kp=self.model.n_keypoints)
             if self.pre_ahead:
                 pipeline.window_pose_tick_reduce(self.traj_args, self.tick_ws, lam=self.gn.lam)
         self.stream.synchronize()

@@ -2,9 +2,20 @@
 
 pa_trajectory_lm_solve against a host-driven loop of the one-step API
 (linearize, gn_step, retract, linearize, D2H of err, decision on the host), max_iters = 10,
-rel_tol = abs_tol = 0 so that both run all 10 iterations on every trajectory."""
+rel_tol = abs_tol = 0 so that both run all 10 iterations on every trajectory.
+
+DESIGN.md 5.5f's: python tools/lm_bench.py --prior [--ab PARENT_LIB] [--rounds N]
+the device solve with and without a marginalization prior on frame 0 (pa_trajectory_lm_prior_solve,
+a random SPD Lambda at the true frame 0), same protocol, at 3 x 6 and 1000 x 24; with --ab also the
+no-prior solve of this build against another build of the library (the parent commit's), one fresh
+process per build and round, alternating on one box (PERSEUS_AMD_LIB_AB, as tools/so_ab.py)."""
+import argparse
+import json
 import os
+import statistics
+import subprocess
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -127,6 +138,118 @@ def bench(T, L, reps):
           "host loop (shared lambda) median", np.median(C), flush=True)
 
 
-print("device", torch.cuda.get_device_name(0), flush=True)
-bench(3, 6, 30)
-bench(1000, 24, 10)
+SHAPES = ((3, 6, 30), (1000, 24, 10))  # T, L, timed runs (5.5b's protocol)
+TOL0 = dict(lm_ref.PARAMS, max_iters=ITERS, rel_tol=0.0, abs_tol=0.0)
+
+
+def solve_times(pr, T, L, reps, with_prior):
+    """{eager, graph: (median, min, max) ms} of the tol-0 device solve on problem `pr`, with a random
+    SPD prior at the true frame 0 (with_prior) or through the parent entry point."""
+    import prior_ref
+
+    y = torch.as_tensor(pr["y"], device=dev)
+    init = {k: torch.as_tensor(pr[k], device=dev) for k in ("pose", "vel", "angvel")}
+    x = {k: v.clone() for k, v in init.items()}
+    a, lin = pipeline.prepare_trajectories(y, x["pose"], x["vel"], x["angvel"], synth.CUBE_CORNERS, synth.CAMERA_K,
+                                           T=T, L=L, **KW)
+    prior = None
+    if with_prior:
+        prior = pipeline.PriorPlan(T=T, L=L, device=dev)
+        info, _ = prior_ref.random_spd(np.random.default_rng(7), T, 10.0)
+        prior.cur["info"].copy_(torch.as_tensor(info))
+        prior.cur["xbar_pose"].copy_(torch.as_tensor(np.asarray(pr["truth"]).reshape(T, L, 12)[:, 0].copy()))
+    plan = pipeline.LMPlan(a, lin, T=T, L=L, **({"prior": prior} if with_prior else {}), **TOL0)
+
+    def reset():
+        for k in x:
+            x[k].copy_(init[k])
+
+    def eager():
+        reset()
+        plan.launch()
+
+    out = {"eager": timed(eager, reps)}
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=torch.cuda.Stream()):
+        plan.launch()
+
+    def graph():
+        reset()
+        g.replay()
+
+    out["graph"] = timed(graph, reps)
+    out["cost"] = float(np.median(plan.out["cost"].cpu().numpy()))
+    return out
+
+
+def load_problems(path):
+    z = np.load(path)
+    return {(T, L): {k: z[f"{T}_{L}_{k}"] for k in ("y", "pose", "vel", "angvel", "truth")} for T, L, _ in SHAPES}
+
+
+def prior_leg(ab, rounds):
+    print("device", torch.cuda.get_device_name(0), flush=True)
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "problems.npz")  # built once: every child process loads them
+        np.savez(path, **{f"{T}_{L}_{k}": v for T, L, _ in SHAPES for k, v in lm_ref.problem(T, L, 0.8).items()})
+        prs = load_problems(path)
+        for T, L, reps in SHAPES:
+            for with_prior in (False, True):
+                r = solve_times(prs[T, L], T, L, reps, with_prior)
+                for form in ("eager", "graph"):
+                    med, lo, hi = r[form]
+                    print(f"T = {T}, L = {L}, {'with a prior' if with_prior else 'no prior   '}, {form}: median "
+                          f"{med:.3f} ms (min {lo:.3f}, max {hi:.3f}); final cost median {r['cost']:.6g}", flush=True)
+        if not ab:
+            return
+        libs = {"parent": os.path.abspath(ab), "this build": pipeline._lib.lib_path()}
+        res = {n: [] for n in libs}
+        for r in range(rounds):
+            for name, lib in libs.items():
+                out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path],
+                                     env=dict(os.environ, PERSEUS_AMD_LIB_AB=lib), capture_output=True, text=True,
+                                     timeout=300)
+                if out.returncode != 0:
+                    print(out.stdout[-2000:], out.stderr[-4000:])
+                    raise SystemExit(f"child failed for {lib}")
+                res[name].append(json.loads(out.stdout.strip().splitlines()[-1]))
+                print(f"round {r} {name}: {res[name][-1]}", flush=True)
+        for key in res["parent"][0]:
+            if key.startswith("cost"):
+                assert len({r[key] for rs in res.values() for r in rs}) == 1, f"{key}: the builds disagree"
+                continue
+            m = {n: statistics.median(r[key] for r in rs) for n, rs in res.items()}
+            sp = {n: (min(r[key] for r in rs), max(r[key] for r in rs)) for n, rs in res.items()}
+            print(f"no prior, {key}: parent {m['parent']:.3f} ms ({sp['parent'][0]:.3f} .. {sp['parent'][1]:.3f}), this "
+                  f"build {m['this build']:.3f} ms ({sp['this build'][0]:.3f} .. {sp['this build'][1]:.3f}), ratio "
+                  f"{m['this build'] / m['parent']:.3f} (medians over {rounds} alternating rounds of per-process medians)")
+        print("final costs of the two builds: bit-identical")
+
+
+def child(path):
+    """One process on the library PERSEUS_AMD_LIB_AB names: the no-prior medians as one JSON line."""
+    prs = load_problems(path)
+    out = {}
+    for T, L, reps in SHAPES:
+        r = solve_times(prs[T, L], T, L, reps, False)
+        out[f"{T}x{L} eager"] = r["eager"][0]
+        out[f"{T}x{L} graph"] = r["graph"][0]
+        out[f"cost {T}x{L}"] = r["cost"].hex()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--prior", action="store_true", help="5.5f: the solve with / without a prior")
+    ap.add_argument("--ab", help="with --prior: another build of the library to time the no-prior solve against")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--child", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        child(args.child)
+    elif args.prior:
+        prior_leg(args.ab, args.rounds)
+    else:
+        print("device", torch.cuda.get_device_name(0), flush=True)
+        bench(3, 6, 30)
+        bench(1000, 24, 10)
