@@ -1,14 +1,13 @@
 // Launchers for the detector kernels (conv.hip).  Precision is a template
 // parameter everywhere: T = _Float16 (fast path) or float (parity path).
 #pragma once
-#include "common.h"
+#include "conv_tile.h"
 
 namespace pa {
 
 // EPI_HEAD (layer4's last conv, conv_gx.h): avgpool + fc in the epilogue instead of the
 // activation store (models.py:31-32)
 enum { EPI_RELU = 1, EPI_RES = 2, EPI_HEAD = 4 };
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Kernel-variant selector per layer (A/B timing; 0 = shipped) and the timestamp buffer
 // of the tracing variants (launch i of a forward gets g_trace + i * TRACE_LAUNCH;

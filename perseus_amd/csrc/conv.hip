@@ -16,49 +16,6 @@
 namespace pa {
 
 // ---------------------------------------------------------------- helpers
-// LDS image of a tile: rows of 128 B (one K-step), 8 chunks of 16 B; chunk c
-// of row r lives at chunk slot c ^ ((r >> 1) & 7).  A 16x16x32 (f16) or
-// 16x16x4 (f32) fragment read has 16 consecutive rows x one chunk per 16-lane
-// group, which this XOR spreads over all 16 bank slots of a 256-B bank row for
-// every ds_read_b128 lane group.
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-template <typename T>
-struct Elem;
-template <>
-struct Elem<_Float16> {
-  static constexpr int KB = 64;  // elements per 128-B K-step
-};
-template <>
-struct Elem<float> {
-  static constexpr int KB = 32;
-};
-
-// One 16-byte K-chunk per lane: lane l holds A[row l&15][chunk l>>4] and
-// B[k][col l&15] for the same k range.
-template <typename T>
-__device__ __forceinline__ void mma16(f32x4& acc, const uint4& a, const uint4& b);
-
-template <>
-__device__ __forceinline__ void mma16<_Float16>(f32x4& acc, const uint4& a, const uint4& b) {
-  half8 ha = __builtin_bit_cast(half8, a);
-  half8 hb = __builtin_bit_cast(half8, b);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha, hb, acc, 0, 0, 0);
-}
-
-template <>
-__device__ __forceinline__ void mma16<float>(f32x4& acc, const uint4& a, const uint4& b) {
-  // The 16 B per lane hold k = 4q..4q+3 (q = lane>>4); MFMA step j consumes
-  // element j of every lane, i.e. k = 4q + j.  A and B use the same permutation
-  // of k, so the sum over k is unchanged.
-  f32x4 fa = __builtin_bit_cast(f32x4, a);
-  f32x4 fb = __builtin_bit_cast(f32x4, b);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[0], fb[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[1], fb[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[2], fb[2], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[3], fb[3], acc, 0, 0, 0);
-}
-
 // 8 consecutive elements <-> f32
 __device__ __forceinline__ void load8(const _Float16* p, float* v) {
   half8 h = *reinterpret_cast<const half8*>(p);
@@ -99,7 +56,7 @@ __device__ __forceinline__ void store8(float* p, const float* v) {
 // NHWC stores, the residual loads and the bias are 16-B coalesced.
 template <typename T, int BM, int BN, int KS>
 __global__ __launch_bounds__(256) void conv_igemm(ConvArgs a) {
-  constexpr int KB = Elem<T>::KB;
+  constexpr int KB = kstep_elems<T>;
   constexpr int CPR = 16 / sizeof(T);
   constexpr int TM = BM / 32, TN = BN / 32;
   constexpr int AR = BM / 32, BR = BN / 32;
@@ -165,9 +122,9 @@ __global__ __launch_bounds__(256) void conv_igemm(ConvArgs a) {
   };
   auto lstore = [&](int buf) {
 #pragma unroll
-    for (int i = 0; i < AR; ++i) *reinterpret_cast<uint4*>(As + buf * BM * 128 + swz(srow + 32 * i, schunk)) = ra[i];
+    for (int i = 0; i < AR; ++i) *reinterpret_cast<uint4*>(As + buf * BM * 128 + tile_swz(srow + 32 * i, schunk)) = ra[i];
 #pragma unroll
-    for (int i = 0; i < BR; ++i) *reinterpret_cast<uint4*>(Bs + buf * BN * 128 + swz(srow + 32 * i, schunk)) = rb[i];
+    for (int i = 0; i < BR; ++i) *reinterpret_cast<uint4*>(Bs + buf * BN * 128 + tile_swz(srow + 32 * i, schunk)) = rb[i];
   };
 
   f32x4 acc[TM][TN];
@@ -187,17 +144,17 @@ __global__ __launch_bounds__(256) void conv_igemm(ConvArgs a) {
     const char* Bb = Bs + buf * BN * 128;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      uint4 fa[TM], fb[TN];
+      u32x4 fa[TM], fb[TN];
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
-        fa[tm] = *reinterpret_cast<const uint4*>(Ab + swz(wr * (BM / 2) + tm * 16 + r16, g * 4 + q));
+        fa[tm] = *reinterpret_cast<const u32x4*>(Ab + tile_swz(wr * (BM / 2) + tm * 16 + r16, g * 4 + q));
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
-        fb[tn] = *reinterpret_cast<const uint4*>(Bb + swz(wc * (BN / 2) + tn * 16 + r16, g * 4 + q));
+        fb[tn] = *reinterpret_cast<const u32x4*>(Bb + tile_swz(wc * (BN / 2) + tn * 16 + r16, g * 4 + q));
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-        for (int tn = 0; tn < TN; ++tn) mma16<T>(acc[tm][tn], fa[tm], fb[tn]);
+        for (int tn = 0; tn < TN; ++tn) mfma16<T>(acc[tm][tn], fa[tm], fb[tn]);
     }
     if (kt + 1 < nk) lstore(buf ^ 1);
     __syncthreads();
@@ -251,7 +208,7 @@ static int run_conv(const ConvArgs& a, hipStream_t s) {
 
 template <typename T>
 int launch_conv(const ConvArgs& a, int ks, hipStream_t s, const char** kname) {
-  constexpr int KB = Elem<T>::KB;
+  constexpr int KB = kstep_elems<T>;
   PA_CHECK(a.Cin % KB == 0, "conv: Cin %d not a multiple of %d", a.Cin, KB);
   PA_CHECK(a.Cout % 64 == 0, "conv: Cout %d not a multiple of 64", a.Cout);
   PA_CHECK(ks == 1 || ks == 3, "conv: kernel size %d", ks);
@@ -357,7 +314,7 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
   for (int kh = 0; kh < 7; ++kh) {
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-      uint4 fa[4], fb[4];
+      uint4 fa[4], fb[4];  // HIP's uint4, cast at the MFMA: loading u32x4 here changes this kernel's register allocation
 #pragma unroll
       for (int tm = 0; tm < 4; ++tm) {
         const int wo = wo_base + tm * 16 + r16;
@@ -372,7 +329,8 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
 #pragma unroll
       for (int tm = 0; tm < 4; ++tm)
 #pragma unroll
-        for (int tn = 0; tn < 4; ++tn) mma16<T>(acc[tm][tn], fa[tm], fb[tn]);
+        for (int tn = 0; tn < 4; ++tn)
+          mfma16<T>(acc[tm][tn], __builtin_bit_cast(u32x4, fa[tm]), __builtin_bit_cast(u32x4, fb[tn]));
     }
   }
   __syncthreads();

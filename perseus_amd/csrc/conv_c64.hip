@@ -10,29 +10,14 @@
 // fragment reads against back-to-back MFMAs (the per-tap barrier of
 // conv_patch.hip is what held layer1 at ~0.25 of peak).
 //
-// Same LDS image conventions as conv_patch.hip: 128-byte rows (a pixel's or an
-// output channel's 64 fp16), 16-byte chunks XOR-swizzled by (row >> 1) & 7,
-// lane -> pixel map frag_off, MFMA A = weights / B = pixels so each lane holds 4
+// LDS images in conv_tile.h's format (swizzled 128-byte rows, lane -> pixel map
+// frag_pixel); MFMA A = weights / B = pixels so each lane holds 4
 // consecutive output channels of one pixel for the register epilogue.
 #include <type_traits>
 
 #include "conv.h"
 
 namespace pa {
-
-typedef unsigned c64u4 __attribute__((ext_vector_type(4)));
-
-template <int V>
-using c64ic = std::integral_constant<int, V>;
-
-// compile-time loop: f(integral_constant<int, I>) for I in [B, E)
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(c64ic<B>{});
-    static_for<B + 1, E>(f);
-  }
-}
 
 namespace c64 {
 constexpr int TH = 16, TW = 16;
@@ -41,16 +26,6 @@ constexpr int PATCHB = NP * 128;                        // 41,472 B
 constexpr int WROWS = 9 * 64;                           // tap-major weight rows
 constexpr int WBYTES = WROWS * 128;                     // 73,728 B
 }  // namespace c64
-
-__device__ __forceinline__ int c64swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int c64frag(int r) { return r < 4 ? 2 * r : (r < 12 ? 2 * (r - 4) + 1 : 2 * (r - 8)); }
-// Output-channel order of the weight rows inside each group of 32: LDS row
-// rho = 16 t + 4 q + v (MFMA tile t of a pair, lane quad q, accumulator slot v)
-// holds channel 8 q + 4 t + v, so a lane's two tiles of a pair cover 8
-// consecutive channels of its pixel -> 16-byte residual loads and output stores.
-__device__ __forceinline__ int c64perm(int rho) {
-  return (rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3);
-}
 
 // DBG (timing-only variants, wrong results): 1 = no MFMA loop, 2 = no next-patch
 // loads (every tile reuses the first patch), 3 = no weight staging; 4 = the
@@ -81,37 +56,37 @@ __global__ __launch_bounds__(WM * 64) void conv3x3_c64(ConvArgs a, int ntiles) {
     constexpr int HALF = (WCH + 1) / 2;  // two batches to bound live registers
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      c64u4 v[HALF];
+      u32x4 v[HALF];
 #pragma unroll
       for (int i = 0; i < HALF; ++i) {
         const int c = tid + (h * HALF + i) * NT;
         if (h * HALF + i < WCH) {
           const int row = c >> 3, ch = c & 7;
           const int tap = row >> 6, co = row & 63;
-          v[i] = *reinterpret_cast<const c64u4*>(w + (size_t)c64perm(co) * 576 + tap * 64 + ch * 8);
+          v[i] = *reinterpret_cast<const u32x4*>(w + (size_t)cout_perm(co) * 576 + tap * 64 + ch * 8);
         }
       }
 #pragma unroll
       for (int i = 0; i < HALF; ++i) {
         const int c = tid + (h * HALF + i) * NT;
-        if (h * HALF + i < WCH) *reinterpret_cast<c64u4*>(wl + c64swz(c >> 3, c & 7)) = v[i];
+        if (h * HALF + i < WCH) *reinterpret_cast<u32x4*>(wl + tile_swz(c >> 3, c & 7)) = v[i];
       }
     }
   }
 
-  c64u4 rp[PCH];
+  u32x4 rp[PCH];
   auto load_patch = [&](int tile) __attribute__((always_inline)) {
     const int img = tile / tpi, rem = tile - (tile / tpi) * tpi;
     const int th0 = (rem / tw_n) * TH, tw0 = (rem - (rem / tw_n) * tw_n) * TW;
 #pragma unroll
     for (int i = 0; i < PCH; ++i) {
       const int c = tid + i * NT;
-      c64u4 v = c64u4{0u, 0u, 0u, 0u};
+      u32x4 v = u32x4{0u, 0u, 0u, 0u};
       const int p = c >> 3, ch = c & 7;
       const int pr = p / PW, pc = p - (p / PW) * PW;
       const int h = th0 + pr - 1, x = tw0 + pc - 1;
       if (c < NP * 8 && tile < ntiles && (unsigned)h < (unsigned)H && (unsigned)x < (unsigned)W)
-        v = *reinterpret_cast<const c64u4*>(in + (((size_t)img * H + h) * W + x) * 64 + ch * 8);
+        v = *reinterpret_cast<const u32x4*>(in + (((size_t)img * H + h) * W + x) * 64 + ch * 8);
       rp[i] = v;
     }
   };
@@ -119,11 +94,11 @@ __global__ __launch_bounds__(WM * 64) void conv3x3_c64(ConvArgs a, int ntiles) {
 #pragma unroll
     for (int i = 0; i < PCH; ++i) {
       const int c = tid + i * NT;
-      if (c < NP * 8) *reinterpret_cast<c64u4*>(patch + buf * PATCHB + c64swz(c >> 3, c & 7)) = rp[i];
+      if (c < NP * 8) *reinterpret_cast<u32x4*>(patch + buf * PATCHB + tile_swz(c >> 3, c & 7)) = rp[i];
     }
   };
 
-  const int o = c64frag(r16);
+  const int o = frag_pixel(r16);
   int ppix[TM];
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
@@ -176,16 +151,16 @@ __global__ __launch_bounds__(WM * 64) void conv3x3_c64(ConvArgs a, int ntiles) {
     const char* pb = patch + buf * PATCHB;
     // 18 (tap, 32-channel half) groups; the fragments of group k+1 are read into
     // the other register set before group k's MFMAs issue (software pipeline).
-    c64u4 fa[2][TN], fb[2][TM];
+    u32x4 fa[2][TN], fb[2][TM];
     auto rd = [&](auto kc) __attribute__((always_inline)) {
       constexpr int K = decltype(kc)::value, TAP = K >> 1, G = K & 1, S = K & 1;
       constexpr int TOFF = (TAP / 3) * PW + (TAP % 3);
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
-        fa[S][tn] = *reinterpret_cast<const c64u4*>(wl + c64swz(TAP * 64 + tn * 16 + r16, G * 4 + q));
+        fa[S][tn] = *reinterpret_cast<const u32x4*>(wl + tile_swz(TAP * 64 + tn * 16 + r16, G * 4 + q));
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
-        fb[S][tm] = *reinterpret_cast<const c64u4*>(pb + c64swz(ppix[tm] + TOFF, G * 4 + q));
+        fb[S][tm] = *reinterpret_cast<const u32x4*>(pb + tile_swz(ppix[tm] + TOFF, G * 4 + q));
     };
     auto mm = [&](auto kc) __attribute__((always_inline)) {
       constexpr int S = decltype(kc)::value & 1;
@@ -198,10 +173,10 @@ __global__ __launch_bounds__(WM * 64) void conv3x3_c64(ConvArgs a, int ntiles) {
                                                                0, 0);
     };
     if constexpr (DBG != 1) {
-    rd(c64ic<0>{});
-    static_for<0, 18>([&](auto kc) __attribute__((always_inline)) {
+    rd(int_c<0>{});
+    const_for<0, 18>([&](auto kc) __attribute__((always_inline)) {
       constexpr int K = decltype(kc)::value;
-      if constexpr (K + 1 < 18) rd(c64ic<K + 1>{});
+      if constexpr (K + 1 < 18) rd(int_c<K + 1>{});
       mm(kc);
     });
     }

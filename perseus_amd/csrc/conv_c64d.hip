@@ -1,5 +1,5 @@
 // Layer1 3x3 stride-1 conv (Cin = Cout = 64), fp16: conv_c64.hip's weight-resident
-// persistent kernel with its staging moved onto LDS-DMA (conv_gx.h's inline-asm
+// persistent kernel with its staging moved onto LDS-DMA (conv_tile.h's inline-asm
 // global_load_lds_dwordx4 and explicit vmcnt waits).
 //
 // conv_c64.hip loads the next tile's 18 x 18 x 64 halo patch into registers at the
@@ -12,10 +12,10 @@
 // per lane) and the first patch are DMA'd in the prologue.
 //
 // LDS: 72 KB weights (row = tap * 64 + permuted output channel) + 2 x 41 KB patch
-// buffers (324 patch pixels rounded up to 41 wave-DMAs of 64 x 16 B), the same
-// 128-byte swizzled rows, lane -> pixel map and channel-pair permutation as
-// conv_gx.h, so the epilogue is c64's.
-#include "conv_gx.h"
+// buffers (324 patch pixels rounded up to 41 wave-DMAs of 64 x 16 B), in conv_tile.h's
+// format (swizzled 128-byte rows, lane -> pixel map, channel permutation), so the
+// epilogue is c64's.
+#include "conv.h"
 
 namespace pa {
 
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64d(ConvArgs a, int ntiles) {
   // division at every call, a divergent branch around the halo select, the zero line's address
   // loaded through the GOT behind an s_waitcnt lgkmcnt(0) that also drained the fragment reads --
   // cost the K loop of every tile ~1.3 us on the younger waves, r05h trace.)
-  const s2w_u4 rsrc = s2w_rsrc(in, (unsigned)((size_t)a.B * H * W * 128 < 0x7fffffffu ? (size_t)a.B * H * W * 128 : 0x7fffffffu));
+  const u32x4 rsrc = s2w_rsrc(in, (unsigned)((size_t)a.B * H * W * 128 < 0x7fffffffu ? (size_t)a.B * H * W * 128 : 0x7fffffffu));
   struct Org {
     int img, h0, x0;  // patch origin of a tile: image, first input row and column (halo included)
     bool on;          // false: no such tile (every lane reads zeros)
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64d(ConvArgs a, int ntiles) {
     s2w_dma16(rsrc, vo, patch + buf * PATCHB + (i < 5 ? i * NWAVE + wid : 5 * NWAVE) * 1024);
   };
 
-  const int o = xfrag(r16);
+  const int o = frag_pixel(r16);
   int ppix[TM];
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64d(ConvArgs a, int ntiles) {
   {
     const int row0 = wid * 8 + (lane >> 3);  // row within the tap
     const int lc = (lane & 7) ^ ((row0 >> 1) & 7);
-    const _Float16* src = w + (size_t)xperm(row0) * 576 + lc * 8;
+    const _Float16* src = w + (size_t)cout_perm(row0) * 576 + lc * 8;
 #pragma unroll
     for (int i = 0; i < 9; ++i) xdma16(src + i * 64, wl + (i * NWAVE + wid) * 1024);
   }
@@ -165,15 +165,15 @@ __global__ __launch_bounds__(512) void conv3x3_c64d(ConvArgs a, int ntiles) {
 #pragma unroll
       for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const char* pb = patch + buf * PATCHB;
-    xu4 fa[2][TN], fb[2][TM];
+    u32x4 fa[2][TN], fb[2][TM];
     auto rd = [&](auto kc) __attribute__((always_inline)) {
       constexpr int K = decltype(kc)::value, TAP = K >> 1, HG = K & 1, S = K & 1;
       constexpr int TOFF = (TAP / 3) * PW + (TAP % 3);
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
-        fa[S][tn] = *reinterpret_cast<const xu4*>(wl + xswz(TAP * 64 + tn * 16 + r16, HG * 4 + q));
+        fa[S][tn] = *reinterpret_cast<const u32x4*>(wl + tile_swz(TAP * 64 + tn * 16 + r16, HG * 4 + q));
 #pragma unroll
-      for (int tm = 0; tm < TM; ++tm) fb[S][tm] = *reinterpret_cast<const xu4*>(pb + xswz(ppix[tm] + TOFF, HG * 4 + q));
+      for (int tm = 0; tm < TM; ++tm) fb[S][tm] = *reinterpret_cast<const u32x4*>(pb + tile_swz(ppix[tm] + TOFF, HG * 4 + q));
     };
     auto mm = [&](auto kc) __attribute__((always_inline)) {
       constexpr int S = decltype(kc)::value & 1;
@@ -184,8 +184,8 @@ __global__ __launch_bounds__(512) void conv3x3_c64d(ConvArgs a, int ntiles) {
           acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, fa[S][tn]),
                                                                __builtin_bit_cast(half8, fb[S][tm]), acc[tm][tn], 0, 0, 0);
     };
-    rd(xic<0>{});
-    gx_for<0, 18>([&](auto kc) __attribute__((always_inline)) {
+    rd(int_c<0>{});
+    const_for<0, 18>([&](auto kc) __attribute__((always_inline)) {
       constexpr int K = decltype(kc)::value;
       if constexpr (K % 2 == 1 && K + 1 < 18) {
         // first tile: tap (K + 1) / 2's weights.  VMEM ops issued after that DMA:
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64d(ConvArgs a, int ntiles) {
           lds_barrier();
         }
       }
-      if constexpr (K + 1 < 18) rd(xic<K + 1>{});
+      if constexpr (K + 1 < 18) rd(int_c<K + 1>{});
       // next tile's patch, one DMA per group from group 0 (wave 0's extra at group 5): issued in
       // the first third of the K loop, so it lands before the tile's end (issued at the odd
       // groups up to 9, the epilogue's vmcnt(0) waited ~0.5 us for the last ones, r05k trace)

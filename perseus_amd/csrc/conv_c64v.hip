@@ -27,7 +27,7 @@
 // patch read of the K loop (ds_read_b128 immediates).  The XOR swizzle of conv_c64d's 128-byte
 // rows needs a VGPR per (row, tap, half) address -- 72 here, which with the weights does not fit
 // in 256.  Conflict-free for ds_read_b128's lane groups (MI355X_MICROARCH.md LDS table): with
-// the xfrag pixel order, a group's q = 0 lanes hit 16-byte bank quads 9 P mod 16 = the even (odd)
+// the frag_pixel pixel order, a group's q = 0 lanes hit 16-byte bank quads 9 P mod 16 = the even (odd)
 // quads and its q = 1 lanes 9 P + 2 mod 16 = the odd (even) ones.  The LDS-DMA writes 64 x 16 B
 // contiguous per wave-instruction, so the pad chunks are DMA'd too (out-of-range offset: zeros).
 //
@@ -36,7 +36,7 @@
 // channel permutation as conv_c64d.hip; each accumulator sums its MFMAs in the same order (tap
 // 0..8, 32-channel halves) and the epilogue is the same (bias, residual, ReLU in f32), so the
 // output is bit-identical to conv_c64d's.
-#include "conv_gx.h"
+#include "conv.h"
 
 namespace pa {
 
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3x3_c64v(ConvArgs a, int ntile
   };
 
   const unsigned abytes = (unsigned)((size_t)a.B * H * W * 128 < 0x7fffffffu ? (size_t)a.B * H * W * 128 : 0x7fffffffu);
-  const s2w_u4 rsrc = s2w_rsrc(in, abytes);
+  const u32x4 rsrc = s2w_rsrc(in, abytes);
   struct Org {
     int img, h0, x0;
     bool on;
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3x3_c64v(ConvArgs a, int ntile
   // residual tile (EPI_RES) by DMA i of each wave: slot c -> tile pixel c >> 3 = i * 8 NWAVE + m
   // (m = 8 wid + lane / 8), slot chunk c & 7 = logical chunk (c & 7) ^ (pixel & 7) (the epilogue's
   // reads are then conflict-free); DMA i adds i * NWAVE / 2 rows to DMA 0's per-lane offset
-  const s2w_u4 rres = s2w_rsrc(a.res ? a.res : a.in, abytes);
+  const u32x4 rres = s2w_rsrc(a.res ? a.res : a.in, abytes);
   const int mres = 8 * wid + (lane >> 3);
   const unsigned rrel = (unsigned)((((mres >> 4) * W + (mres & 15)) * 64 + (((lane & 7) ^ (mres & 7)) * 8)) * 2);
   auto dma_res = [&](int i, int img, int th0, int tw0, int rb) __attribute__((always_inline)) {
@@ -192,16 +192,16 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3x3_c64v(ConvArgs a, int ntile
     s2w_dma16(rres, tb + rrel, resb(rb) + (i * NWAVE + wid) * 1024);
   };
 
-  const int o = xfrag(r16);
+  const int o = frag_pixel(r16);
   // this lane's patch-read base: pixel (row 4 wm, column o), chunk position 2 q
   const unsigned rbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)patch + (unsigned)((wm * 4 * PW + o) * PXB + q * 32);
   if (tid < 64) bias_l[tid] = a.bias[tid];  // read back in the epilogue (8 VGPRs not held through the K loop)
   __builtin_amdgcn_sched_barrier(0);
 
   // prologue: the first tile's patch; the weights by LDS-DMA (conv_c64d.hip's layout: row
-  // tap * 64 + rho holds channel xperm(rho), 16-byte chunks XOR-swizzled), once per workgroup, in
+  // tap * 64 + rho holds channel cout_perm(rho), 16-byte chunks XOR-swizzled), once per workgroup, in
   // rounds of WROUND taps; every wave reads its 36 fragments: (K, tn) = channel
-  // xperm(32 wn + 16 tn + r16), tap K / 2, input channels 32 (K & 1) + 8 q .. + 7.  (Loading them
+  // cout_perm(32 wn + 16 tn + r16), tap K / 2, input channels 32 (K & 1) + 8 q .. + 7.  (Loading them
   // straight into VGPRs had the waves of a channel half fetch the same bytes from L2: 295 KB per
   // workgroup, a 10 us prologue, r05q trace.)
   int j = blockIdx.x;
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3x3_c64v(ConvArgs a, int ntile
       for (int i = 0; i < RDW; ++i) dma_res(i, o0.img, o0.h0 + 1, o0.x0 + 1, 0);
     }
   }
-  xu4 wr[18][TN];
+  u32x4 wr[18][TN];
   {
     constexpr int DPT = 8 / NWAVE;  // DMAs (8 rows of 128 B each) per wave per tap
     static_assert(DPT * NWAVE * 1024 == 64 * 128, "weight DMA split");
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3x3_c64v(ConvArgs a, int ntile
         for (int d = 0; d < DPT; ++d) {
           const int row0 = (d * NWAVE + wid) * 8 + (lane >> 3);  // row within the tap
           const int lc = (lane & 7) ^ ((row0 >> 1) & 7);
-          xdma16(w + (size_t)xperm(row0) * 576 + tap * 64 + lc * 8, wst + ((tap - T0) * 8 + d * NWAVE + wid) * 1024);
+          xdma16(w + (size_t)cout_perm(row0) * 576 + tap * 64 + lc * 8, wst + ((tap - T0) * 8 + d * NWAVE + wid) * 1024);
         }
       xwait_vm<0>();
       lds_barrier();
@@ -242,14 +242,14 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3x3_c64v(ConvArgs a, int ntile
       for (int k = 2 * T0; k < 2 * T1; ++k)
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn)
-          wr[k][tn] = *reinterpret_cast<const xu4*>(wst + xswz(((k >> 1) - T0) * 64 + wn * 32 + tn * 16 + r16, (k & 1) * 4 + q));
+          wr[k][tn] = *reinterpret_cast<const u32x4*>(wst + tile_swz(((k >> 1) - T0) * 64 + wn * 32 + tn * 16 + r16, (k & 1) * 4 + q));
       lds_barrier();  // reads retired before the staging area is rewritten
     };
     if constexpr (G::WROUND >= 9) {
-      stage(xic<0>{}, xic<9>{});
+      stage(int_c<0>{}, int_c<9>{});
     } else {
-      stage(xic<0>{}, xic<G::WROUND>{});
-      stage(xic<G::WROUND>{}, xic<9>{});
+      stage(int_c<0>{}, int_c<G::WROUND>{});
+      stage(int_c<G::WROUND>{}, int_c<9>{});
     }
   }
   if constexpr (DBG == 4) trace_stamp(a.trace, 1);
@@ -283,13 +283,13 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3x3_c64v(ConvArgs a, int ntile
       for (int k = 0; k < TN; ++k) acc[i][k] = f32x4{0.f, 0.f, 0.f, 0.f};
     const __attribute__((address_space(3))) char* pb =
         (const __attribute__((address_space(3))) char*)(size_t)(rbase + buf * BSTR);
-    xu4 fb[2][TM];
+    u32x4 fb[2][TM];
     auto rd = [&](auto kc) __attribute__((always_inline)) {
       constexpr int K = decltype(kc)::value, TAP = K >> 1, HG = K & 1, S = K & 1;
       constexpr int TOFF = (TAP / 3) * PW + (TAP % 3);
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
-        fb[S][tm] = *reinterpret_cast<const __attribute__((address_space(3))) xu4*>(pb + (tm * PW + TOFF) * PXB + HG * 16);
+        fb[S][tm] = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(pb + (tm * PW + TOFF) * PXB + HG * 16);
     };
     auto mm = [&](auto kc) __attribute__((always_inline)) {
       constexpr int K = decltype(kc)::value, S = K & 1;
@@ -303,10 +303,10 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3x3_c64v(ConvArgs a, int ntile
     if constexpr (DYN) {  // the tile after next (its return is first used after the K loop's wait)
       if (tid == 0 && has_next) kdyn = atomicAdd(a.cnt + x8, 1u);
     }
-    rd(xic<0>{});
-    gx_for<0, 18>([&](auto kc) __attribute__((always_inline)) {
+    rd(int_c<0>{});
+    const_for<0, 18>([&](auto kc) __attribute__((always_inline)) {
       constexpr int K = decltype(kc)::value;
-      if constexpr (K + 1 < 18) rd(xic<K + 1>{});
+      if constexpr (K + 1 < 18) rd(int_c<K + 1>{});
       __builtin_amdgcn_sched_barrier(0);  // next group's reads ahead of this group's MFMAs
       if constexpr (K < PDW) {  // next tile's patch, one DMA per group
         __builtin_amdgcn_sched_barrier(0);

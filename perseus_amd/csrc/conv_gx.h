@@ -1,8 +1,7 @@
 // 3x3 stride-1 conv, fp16, LDS-DMA staging with a deep weight ring (the layer2-4
-// BasicBlock convs).  LDS images: 128-byte rows (one pixel's or one output
-// channel's 64 fp16 of the current 64-channel block), 16-byte chunks XOR-swizzled
-// by (row >> 1) & 7; the halo patch is DMA'd with the swizzle applied to the
-// per-lane source address.  MFMA A = weights, B = pixels; register epilogue.  An
+// BasicBlock convs).  LDS images in conv_tile.h's format; the halo patch is DMA'd
+// with the swizzle applied to the per-lane source address.  MFMA A = weights,
+// B = pixels; register epilogue.  An
 // earlier version of this kernel (distance-2 ring, looped K) measured 22 us on
 // layer3 against this one's 19.5.  The design points:
 //
@@ -39,79 +38,6 @@
 #include "conv.h"
 
 namespace pa {
-
-typedef unsigned xu4 __attribute__((ext_vector_type(4)));
-
-template <int V>
-using xic = std::integral_constant<int, V>;
-
-template <int B, int E, typename F>
-__device__ __forceinline__ void gx_for(F&& f) {
-  if constexpr (B < E) {
-    f(xic<B>{});
-    gx_for<B + 1, E>(f);
-  }
-}
-
-// 128 zero bytes (halo source); one copy per translation unit (no relocatable device code)
-static __device__ __attribute__((aligned(128))) unsigned gx_zero_line[32];
-
-__device__ __forceinline__ int xswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int xfrag(int r) { return r < 4 ? 2 * r : (r < 12 ? 2 * (r - 4) + 1 : 2 * (r - 8)); }
-// weight row 16 t + 4 q + v of each 32-row group holds channel 8 q + 4 t + v: a
-// lane's tile pair covers 8 consecutive channels (16-byte epilogue accesses)
-__device__ __forceinline__ int xperm(int rho) {
-  return (rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3);
-}
-
-template <int N>
-__device__ __forceinline__ void xwait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (0x7 << 4) | (0xF << 8));
-#endif
-}
-// 16 B per lane global -> LDS (wave-uniform LDS base + lane * 16), as inline asm:
-// with the builtin, hipcc's waitcnt pass stops counting LDS reads in order once an
-// LDS-DMA is pending and waits lgkmcnt(0) at the next use of any LDS read (every
-// step, right after the barrier).  The pass does not see these VMEM ops, so every
-// wait for DMA'd data is the explicit xwait_vm; its own vmcnt waits (bias,
-// residual) only get more conservative.  M0 write -> LDS-DMA needs one wait state.
-__device__ __forceinline__ void xdma16(const void* src, char* lds) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const unsigned off = __builtin_amdgcn_readfirstlane(
-      (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"  // m0 is reserved: nothing else in these kernels keeps it live
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(off), "v"(src) : "memory", "m0");
-#pragma clang diagnostic pop
-#endif
-}
-
-// 16 B per lane from a buffer resource -> LDS (wave-uniform LDS base + lane * 16), as inline
-// asm like xdma16 (its waits are explicit).  A lane whose 32-bit byte offset is
-// out of the resource's range (S2W_OOB) reads zeros: the halo needs no pointer select and
-// the per-lane address is one 32-bit VGPR (the 64-bit pointer math of xdma16 kept ~75
-// VGPRs live across this kernel's unrolled loop and spilled).
-typedef unsigned s2w_u4 __attribute__((ext_vector_type(4)));
-constexpr unsigned S2W_OOB = 0x80000000u;
-__device__ __forceinline__ s2w_u4 s2w_rsrc(const void* base, unsigned bytes) {
-  // wave-uniform by construction; readfirstlane puts it in SGPRs for the asm's "s" operand
-  const unsigned long long b = (unsigned long long)base;
-  return s2w_u4{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b),
-                (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32) & 0xffffu),
-                (unsigned)__builtin_amdgcn_readfirstlane(bytes), 0x00020000u};
-}
-__device__ __forceinline__ void s2w_dma16(s2w_u4 rsrc, unsigned voff, char* lds) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const unsigned off = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)lds);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"  // m0 is reserved: nothing else in these kernels keeps it live
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(off), "v"(voff),
-               "s"(rsrc) : "memory", "m0");
-#pragma clang diagnostic pop
-#endif
-}
 
 // Issue schedule (per wave), used at compile time.
 struct GxPlan {
@@ -282,15 +208,6 @@ __device__ __forceinline__ constexpr int gx_boff(int b) {
   return b < NCB ? b * 64 : CF + (b - NCB) * 64;
 }
 
-// hi / lo fp16 pair of an f32 value (hi + lo == v to 2^-22 relative)
-struct HiLo {
-  _Float16 hi, lo;
-};
-__device__ __forceinline__ HiLo split_x3(float v) {
-  const _Float16 h = (_Float16)v;
-  return HiLo{h, (_Float16)(v - (float)h)};
-}
-
 // PART = NS > 0 (split-K for small batches, conv_splitk.hip): the workgroup runs the CIN
 // (= 64 * NCB) input channels of split blockIdx.y of an a.Cin = NS * CIN channel conv and
 // writes its f32 accumulators to a.part[split] -- no bias, residual or ReLU (splitk_reduce
@@ -397,7 +314,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv3x3_gx(ConvArgs a, int 
   // patch DMAs through a buffer resource over this tile's images: one 32-bit byte offset per lane
   // and DMA, computed once; a block adds a constant; halo / padding lanes hold an out-of-range
   // offset (S2W_OOB + a block offset stays out of range) and read zeros (no pointer select)
-  const s2w_u4 prs = s2w_rsrc((const _Float16*)a.in + (size_t)img0 * H * W * kin,
+  const u32x4 prs = s2w_rsrc((const _Float16*)a.in + (size_t)img0 * H * W * kin,
                               (unsigned)((size_t)(a.B - img0 < NI ? a.B - img0 : NI) * H * W * kin * 2));
   unsigned poff[PDMA];
 #pragma unroll
@@ -421,7 +338,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv3x3_gx(ConvArgs a, int 
   for (int i = 0; i < WDMA; ++i) {
     const int c = (i * NW + wid) * 64 + lane;
     const int co = c >> 3, lc = (c & 7) ^ ((co >> 1) & 7);
-    wsrc[i] = w + (size_t)(n0 + xperm(co)) * (9 * kin) + lc * 8;
+    wsrc[i] = w + (size_t)(n0 + cout_perm(co)) * (9 * kin) + lc * 8;
   }
   auto dma_w = [&](int s) __attribute__((always_inline)) {
     const int vb = s / 9, tap = s % 9;
@@ -435,7 +352,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv3x3_gx(ConvArgs a, int 
                wring + (s % NSLOT) * WSLOT + WB + (i * NW + wid) * 1024);
   };
 
-  const int o = xfrag(r16);
+  const int o = frag_pixel(r16);
   int ppix[TM];
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
@@ -510,8 +427,8 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv3x3_gx(ConvArgs a, int 
   // reads into set k % (FD + 1) while the MFMAs of an earlier sub-step run
   static_assert(FD == 1 || FD == 2, "fragment distance");
   constexpr int NSET = FD + 1;
-  xu4 fa[NSET][TN], fb[NSET][TM];
-  xu4 fa2[XM ? NSET : 1][XM ? TN : 1];  // XM: the second weight tile's fragments
+  u32x4 fa[NSET][TN], fb[NSET][TM];
+  u32x4 fa2[XM ? NSET : 1][XM ? TN : 1];  // XM: the second weight tile's fragments
   auto read_frags = [&](auto kc) __attribute__((always_inline)) {
     constexpr int K = decltype(kc)::value;
     constexpr int S = K >> 1, HG = K & 1, CB = S / 9, TAP = S % 9, SET = K % NSET;
@@ -520,13 +437,13 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv3x3_gx(ConvArgs a, int 
     const char* wb = wring + (S % NSLOT) * WSLOT;
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn)
-      fa[SET][tn] = *reinterpret_cast<const xu4*>(wb + xswz(wn * WTN + tn * 16 + r16, HG * 4 + q));
+      fa[SET][tn] = *reinterpret_cast<const u32x4*>(wb + tile_swz(wn * WTN + tn * 16 + r16, HG * 4 + q));
     if constexpr (VB::two(CB))
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
-        fa2[SET][tn] = *reinterpret_cast<const xu4*>(wb + WB + xswz(wn * WTN + tn * 16 + r16, HG * 4 + q));
+        fa2[SET][tn] = *reinterpret_cast<const u32x4*>(wb + WB + tile_swz(wn * WTN + tn * 16 + r16, HG * 4 + q));
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm) fb[SET][tm] = *reinterpret_cast<const xu4*>(pb + xswz(ppix[tm] + TOFF, HG * 4 + q));
+    for (int tm = 0; tm < TM; ++tm) fb[SET][tm] = *reinterpret_cast<const u32x4*>(pb + tile_swz(ppix[tm] + TOFF, HG * 4 + q));
   };
   auto mfma = [&](auto kc) __attribute__((always_inline)) {
     constexpr int K = decltype(kc)::value;
@@ -558,13 +475,13 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv3x3_gx(ConvArgs a, int 
     const char* wb = wring + (S % NSLOT) * WSLOT;
     const int ch = kg * 4 + q;
 #pragma unroll
-    for (int tn = 0; tn < TN; ++tn) fa[SET][tn] = *reinterpret_cast<const xu4*>(wb + xswz(wn * WTN + tn * 16 + r16, ch));
+    for (int tn = 0; tn < TN; ++tn) fa[SET][tn] = *reinterpret_cast<const u32x4*>(wb + tile_swz(wn * WTN + tn * 16 + r16, ch));
     if constexpr (VB::two(CB))
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
-        fa2[SET][tn] = *reinterpret_cast<const xu4*>(wb + WB + xswz(wn * WTN + tn * 16 + r16, ch));
+        fa2[SET][tn] = *reinterpret_cast<const u32x4*>(wb + WB + tile_swz(wn * WTN + tn * 16 + r16, ch));
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm) fb[SET][tm] = *reinterpret_cast<const xu4*>(pb + xswz(ppix[tm] + TOFF, ch));
+    for (int tm = 0; tm < TM; ++tm) fb[SET][tm] = *reinterpret_cast<const u32x4*>(pb + tile_swz(ppix[tm] + TOFF, ch));
   };
   // KS = 2: rows [T0, T1) of step S's MFMAs (XM: x_hi w_lo after x_hi w_hi, as mfma())
   auto mfma_k = [&](auto sc, auto t0, auto t1) __attribute__((always_inline)) {
@@ -585,14 +502,14 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv3x3_gx(ConvArgs a, int 
                                                                __builtin_bit_cast(half8, fb[SET][tm]), acc[tm][tn], 0, 0, 0);
   };
   if constexpr (KS == 2) {
-    read_frags_k(xic<0>{});
-    gx_for<0, NSTEPS>([&](auto sc) __attribute__((always_inline)) {
+    read_frags_k(int_c<0>{});
+    const_for<0, NSTEPS>([&](auto sc) __attribute__((always_inline)) {
       constexpr int S = decltype(sc)::value;
       constexpr int CB = S / 9;
       // step S + 1's data landed before the barrier that closed step S - 1 (as FD = 2)
-      if constexpr (S + 1 < NSTEPS) read_frags_k(xic<S + 1>{});
+      if constexpr (S + 1 < NSTEPS) read_frags_k(int_c<S + 1>{});
       __builtin_amdgcn_s_setprio(1);
-      mfma_k(sc, xic<0>{}, xic<TM / 2>{});
+      mfma_k(sc, int_c<0>{}, int_c<TM / 2>{});
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (S + PD < NSTEPS) dma_w(S + PD);
@@ -603,7 +520,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv3x3_gx(ConvArgs a, int 
       }
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_setprio(1);
-      mfma_k(sc, xic<TM / 2>{}, xic<TM>{});
+      mfma_k(sc, int_c<TM / 2>{}, int_c<TM>{});
       __builtin_amdgcn_s_setprio(0);
       if constexpr ((S + 1) % G == 0 && S + 2 < NSTEPS) {
         constexpr int V = S + G + 1 < NSTEPS ? S + G + 1 : NSTEPS - 1;
@@ -612,17 +529,17 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv3x3_gx(ConvArgs a, int 
       }
     });
   } else {
-  read_frags(xic<0>{});
-  if constexpr (FD == 2) read_frags(xic<1>{});
-  gx_for<0, (DBG == 3 ? 0 : NSTEPS)>([&](auto sc) __attribute__((always_inline)) {
+  read_frags(int_c<0>{});
+  if constexpr (FD == 2) read_frags(int_c<1>{});
+  const_for<0, (DBG == 3 ? 0 : NSTEPS)>([&](auto sc) __attribute__((always_inline)) {
     constexpr int S = decltype(sc)::value;
     constexpr int CB = S / 9, TAP = S % 9;
-    if constexpr (FD == 1) read_frags(xic<2 * S + 1>{});
-    else if constexpr (S + 1 < NSTEPS) read_frags(xic<2 * S + 2>{});
+    if constexpr (FD == 1) read_frags(int_c<2 * S + 1>{});
+    else if constexpr (S + 1 < NSTEPS) read_frags(int_c<2 * S + 2>{});
     __builtin_amdgcn_s_setprio(1);
-    mfma(xic<2 * S>{});
+    mfma(int_c<2 * S>{});
     __builtin_amdgcn_s_setprio(0);
-    if constexpr (S + 1 < NSTEPS) read_frags(xic<2 * S + 1 + FD>{});
+    if constexpr (S + 1 < NSTEPS) read_frags(int_c<2 * S + 1 + FD>{});
     // DMAs after this step's LDS reads (they are issued by then; see xdma16)
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (S + PD < NSTEPS && (DBG < 2 || DBG == 5)) dma_w(S + PD);
@@ -635,7 +552,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv3x3_gx(ConvArgs a, int 
     }
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
-    mfma(xic<2 * S + 1>{});
+    mfma(int_c<2 * S + 1>{});
     __builtin_amdgcn_s_setprio(0);
     if constexpr ((S + 1) % G == 0 && S + 2 < NSTEPS && (DBG == 0 || DBG == 4 || DBG == 5 || DBG == 6)) {
       // the next group (steps s+1 .. s+G) reads the fragments of steps up to s+G+1

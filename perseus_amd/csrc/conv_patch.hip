@@ -19,38 +19,6 @@
 
 namespace pa {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-struct PElem;
-template <>
-struct PElem<_Float16> {
-  static constexpr int KB = 64;
-};
-template <>
-struct PElem<float> {
-  static constexpr int KB = 32;
-};
-
-__device__ __forceinline__ int pswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-template <typename T>
-__device__ __forceinline__ void pmma(f32x4& acc, const u32x4& a, const u32x4& b);
-
-template <>
-__device__ __forceinline__ void pmma<_Float16>(f32x4& acc, const u32x4& a, const u32x4& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), acc, 0, 0,
-                                               0);
-}
-template <>
-__device__ __forceinline__ void pmma<float>(f32x4& acc, const u32x4& a, const u32x4& b) {
-  f32x4 fa = __builtin_bit_cast(f32x4, a), fb = __builtin_bit_cast(f32x4, b);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[0], fb[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[1], fb[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[2], fb[2], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[3], fb[3], acc, 0, 0, 0);
-}
-
 // 4 consecutive elements <-> f32
 __device__ __forceinline__ void ld4(const _Float16* p, float* v) {
   half4 h = *reinterpret_cast<const half4*>(p);
@@ -78,15 +46,6 @@ __device__ __forceinline__ void st4(float* p, const float* v) {
   *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
 }
 
-// Lane -> pixel map of a 16-pixel MFMA fragment: lanes whose ds_read_b128 lane
-// groups read chunk c0 take the even pixel offsets, the others the odd ones, so
-// with the (p >> 1) & 7 XOR swizzle every 16-lane group hits 16 distinct bank
-// slots for ANY starting pixel (the 9 taps shift the start by 1 and by PW).
-__device__ __forceinline__ int frag_off(int r) { return r < 4 ? 2 * r : (r < 12 ? 2 * (r - 4) + 1 : 2 * (r - 8)); }
-
-template <int V>
-using ic = std::integral_constant<int, V>;
-
 // KSP = 2: intra-workgroup split-K -- two groups of WM x WN waves compute the
 // same output tile, group kg reading only channel half kg of every 64-channel
 // block (half the fragment reads per MFMA of a KSP = 1 wave with the same tile,
@@ -96,7 +55,7 @@ template <typename T, int TH, int TW, int NI, int BN, int WM, int WN, int PBUF, 
 __global__ __launch_bounds__(WM* WN * 64 * KSP) void conv3x3_patch(ConvArgs a, int ntiles) {
   constexpr int NT = WM * WN * 64 * KSP;
   static_assert(KSP == 1 || (KSP == 2 && TPW == 1), "split-K: one tile per workgroup");
-  constexpr int KB = PElem<T>::KB;
+  constexpr int KB = kstep_elems<T>;
   constexpr int CPR = 16 / sizeof(T);
   constexpr int NCB = CIN / KB;  // 128-byte channel blocks
   constexpr int SPC = 9;         // steps (filter taps) per channel block
@@ -175,7 +134,7 @@ __global__ __launch_bounds__(WM* WN * 64 * KSP) void conv3x3_patch(ConvArgs a, i
 #pragma unroll
     for (int i = 0; i < PCH; ++i) {
       const int c = tid + i * NT;
-      if (c < NP * 8) *reinterpret_cast<u32x4*>(patch + buf * PATCHB + pswz(c >> 3, c & 7)) = rp[i];
+      if (c < NP * 8) *reinterpret_cast<u32x4*>(patch + buf * PATCHB + tile_swz(c >> 3, c & 7)) = rp[i];
     }
   };
   auto load_w = [&](int s, auto setc) __attribute__((always_inline)) {
@@ -193,12 +152,12 @@ __global__ __launch_bounds__(WM* WN * 64 * KSP) void conv3x3_patch(ConvArgs a, i
 #pragma unroll
     for (int i = 0; i < BCH; ++i) {
       const int c = tid + i * NT;
-      *reinterpret_cast<u32x4*>(wbuf + buf * WB + pswz(c >> 3, c & 7)) = rb[SET][i];
+      *reinterpret_cast<u32x4*>(wbuf + buf * WB + tile_swz(c >> 3, c & 7)) = rb[SET][i];
     }
   };
 
   // per-lane patch pixel (tap (0,0)) of each pixel fragment (tile independent)
-  const int o = frag_off(r16);
+  const int o = frag_pixel(r16);
   int ppix[TM];
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
@@ -225,11 +184,11 @@ __global__ __launch_bounds__(WM* WN * 64 * KSP) void conv3x3_patch(ConvArgs a, i
                            : (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
 
   load_patch(cur, 0);
-  load_w(0, ic<0>{});
+  load_w(0, int_c<0>{});
   store_patch(0);
-  store_w(0, ic<0>{});
-  load_w(NSTEPS > 1 ? 1 : 0, ic<1>{});
-  load_w(NSTEPS > 2 ? 2 : 0, ic<2>{});
+  store_w(0, int_c<0>{});
+  load_w(NSTEPS > 1 ? 1 : 0, int_c<1>{});
+  load_w(NSTEPS > 2 ? 2 : 0, int_c<2>{});
   __syncthreads();
 
   // Weight-step index runs on across tiles (W(s) of tile t+1 = W(s) of tile t),
@@ -260,7 +219,7 @@ __global__ __launch_bounds__(WM* WN * 64 * KSP) void conv3x3_patch(ConvArgs a, i
       const int s = cb * SPC + ST;
       int sw = s + WD;
       if (sw >= NSTEPS) sw = more ? sw - NSTEPS : NSTEPS - 1;
-      load_w(sw, ic<ST % WD>{});
+      load_w(sw, int_c<ST % WD>{});
       const bool last_cb = cb + 1 == NCB;
       if constexpr (ST == 0 && (NCB > 1 || TPW > 1)) {
         // next channel block, or the next tile's block 0 (clamped: this tile's
@@ -277,18 +236,18 @@ __global__ __launch_bounds__(WM* WN * 64 * KSP) void conv3x3_patch(ConvArgs a, i
         const int gc = (KSP == 2 ? kg : g) * 4 + q;
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn)
-          fa[g][tn] = *reinterpret_cast<const u32x4*>(wb + pswz(wn * WTN + tn * 16 + r16, gc));
+          fa[g][tn] = *reinterpret_cast<const u32x4*>(wb + tile_swz(wn * WTN + tn * 16 + r16, gc));
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
-          fb[g][tm] = *reinterpret_cast<const u32x4*>(pb + pswz(ppix[tm] + toff, gc));
+          fb[g][tm] = *reinterpret_cast<const u32x4*>(pb + tile_swz(ppix[tm] + toff, gc));
       }
 #pragma unroll
       for (int g = 0; g < NG; ++g)
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-          for (int tn = 0; tn < TN; ++tn) pmma<T>(acc[tm][tn], fa[g][tn], fb[g][tm]);
-      store_w((gs + 1) & 1, ic<(ST + 1) % WD>{});
+          for (int tn = 0; tn < TN; ++tn) mfma16<T>(acc[tm][tn], fa[g][tn], fb[g][tm]);
+      store_w((gs + 1) & 1, int_c<(ST + 1) % WD>{});
       ++gs;
       if constexpr (ST == SPC - 1 && (NCB > 1 || TPW > 1)) {
         if (!last_cb || more) {
@@ -306,15 +265,15 @@ __global__ __launch_bounds__(WM* WN * 64 * KSP) void conv3x3_patch(ConvArgs a, i
       __syncthreads();
     };
     for (int cb = 0; cb < NCB; ++cb) {
-      step(cb, ic<0>{});
-      step(cb, ic<1>{});
-      step(cb, ic<2>{});
-      step(cb, ic<3>{});
-      step(cb, ic<4>{});
-      step(cb, ic<5>{});
-      step(cb, ic<6>{});
-      step(cb, ic<7>{});
-      step(cb, ic<8>{});
+      step(cb, int_c<0>{});
+      step(cb, int_c<1>{});
+      step(cb, int_c<2>{});
+      step(cb, int_c<3>{});
+      step(cb, int_c<4>{});
+      step(cb, int_c<5>{});
+      step(cb, int_c<6>{});
+      step(cb, int_c<7>{});
+      step(cb, int_c<8>{});
       if constexpr (BLOCKED) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -426,7 +385,7 @@ thread_local unsigned long long* g_trace = nullptr;
 template <typename T>
 int launch_conv3x3_s1(const ConvArgs& a, hipStream_t s, const char** kname) {
   PA_CHECK(a.stride == 1 && a.pad == 1 && a.Hin == a.Hout && a.Win == a.Wout, "patch conv: stride-1 only");
-  PA_CHECK(a.Cin % PElem<T>::KB == 0, "patch conv: Cin %d", a.Cin);
+  PA_CHECK(a.Cin % kstep_elems<T> == 0, "patch conv: Cin %d", a.Cin);
   if (a.B <= 0) return PA_OK;
   if constexpr (std::is_same<T, _Float16>::value) {
     const int layer = a.Hout == 64 ? 1 : a.Hout == 32 ? 2 : a.Hout == 16 ? 3 : 4;

@@ -10,7 +10,7 @@
 // Patch: (2TH+1) x (2TW+1) input pixels per image, columns stored de-interleaved
 // (even input columns first, then odd) so that the stride-2 window of 16
 // consecutive output columns reads 16 consecutive LDS pixels for every tap
-// (conflict-free with the frag_off lane map and the (p>>1)&7 swizzle, as in
+// (conflict-free with conv_tile.h's lane map and swizzle, as in
 // conv_patch.hip).  Weights stream per tap (3 register sets, LDS ring of 2),
 // the downsample tile is loaded at tap 1 and staged at tap 3 of each channel
 // block; one patch buffer (refilled at channel-block boundaries from registers
@@ -20,41 +20,6 @@
 #include "conv.h"
 
 namespace pa {
-
-typedef unsigned s2u4 __attribute__((ext_vector_type(4)));
-
-template <int V>
-using sc = std::integral_constant<int, V>;
-
-template <typename T>
-struct SElem;
-template <>
-struct SElem<_Float16> {
-  static constexpr int KB = 64;
-};
-template <>
-struct SElem<float> {
-  static constexpr int KB = 32;
-};
-
-__device__ __forceinline__ int s2swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int s2frag_off(int r) { return r < 4 ? 2 * r : (r < 12 ? 2 * (r - 4) + 1 : 2 * (r - 8)); }
-
-template <typename T>
-__device__ __forceinline__ void s2mma(f32x4& acc, const s2u4& a, const s2u4& b);
-template <>
-__device__ __forceinline__ void s2mma<_Float16>(f32x4& acc, const s2u4& a, const s2u4& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), acc, 0, 0,
-                                               0);
-}
-template <>
-__device__ __forceinline__ void s2mma<float>(f32x4& acc, const s2u4& a, const s2u4& b) {
-  f32x4 fa = __builtin_bit_cast(f32x4, a), fb = __builtin_bit_cast(f32x4, b);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[0], fb[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[1], fb[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[2], fb[2], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[3], fb[3], acc, 0, 0, 0);
-}
 
 template <typename T>
 struct S2R4;
@@ -70,7 +35,7 @@ struct S2R4<float> {
 template <typename T, int TH, int TW, int NI, int BN, int WM, int WN, int CIN>
 __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
   constexpr int NT = WM * WN * 64;
-  constexpr int KB = SElem<T>::KB;
+  constexpr int KB = kstep_elems<T>;
   constexpr int CPR = 16 / sizeof(T);
   constexpr int NCB = CIN / KB;
   constexpr int NSTEPS = NCB * 9;
@@ -111,14 +76,14 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
   const int th0 = (rem / tw_n) * TH, tw0 = (rem - (rem / tw_n) * tw_n) * TW;
   const int n0 = tn_idx * BN;
 
-  s2u4 rp[PCH];
-  s2u4 rb[3][BCH];
-  s2u4 rds[BCH];
+  u32x4 rp[PCH];
+  u32x4 rb[3][BCH];
+  u32x4 rds[BCH];
   auto load_patch = [&](int cb) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < PCH; ++i) {
       const int c = tid + i * NT;
-      s2u4 v = s2u4{0u, 0u, 0u, 0u};
+      u32x4 v = u32x4{0u, 0u, 0u, 0u};
       if (c < NP * 8) {
         const int p = c >> 3, ch = c & 7;
         const int img = p / IMS, pp = p - (p / IMS) * IMS;
@@ -126,7 +91,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
         const int col = pos <= TW ? 2 * pos : 2 * (pos - TW - 1) + 1;  // de-interleaved columns
         const int n = img0 + img, h = 2 * th0 - 1 + pr, x = 2 * tw0 - 1 + col;
         if (pr < PH && n < a.B && (unsigned)h < (unsigned)Hin && (unsigned)x < (unsigned)Win)
-          v = *reinterpret_cast<const s2u4*>(in + (((size_t)n * Hin + h) * Win + x) * CIN + cb * KB + ch * CPR);
+          v = *reinterpret_cast<const u32x4*>(in + (((size_t)n * Hin + h) * Win + x) * CIN + cb * KB + ch * CPR);
       }
       rp[i] = v;
     }
@@ -135,7 +100,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
 #pragma unroll
     for (int i = 0; i < PCH; ++i) {
       const int c = tid + i * NT;
-      if (c < NP * 8) *reinterpret_cast<s2u4*>(patch + s2swz(c >> 3, c & 7)) = rp[i];
+      if (c < NP * 8) *reinterpret_cast<u32x4*>(patch + tile_swz(c >> 3, c & 7)) = rp[i];
     }
   };
   auto load_w = [&](int s, auto setc) __attribute__((always_inline)) {
@@ -145,7 +110,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
 #pragma unroll
     for (int i = 0; i < BCH; ++i) {
       const int c = tid + i * NT;
-      rb[SET][i] = *reinterpret_cast<const s2u4*>(w + (size_t)(n0 + (c >> 3)) * KTOT + tap * CIN + cb * KB + (c & 7) * CPR);
+      rb[SET][i] = *reinterpret_cast<const u32x4*>(w + (size_t)(n0 + (c >> 3)) * KTOT + tap * CIN + cb * KB + (c & 7) * CPR);
     }
   };
   auto store_w = [&](int buf, auto setc) __attribute__((always_inline)) {
@@ -153,26 +118,26 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
 #pragma unroll
     for (int i = 0; i < BCH; ++i) {
       const int c = tid + i * NT;
-      *reinterpret_cast<s2u4*>(wbuf + buf * WB + s2swz(c >> 3, c & 7)) = rb[SET][i];
+      *reinterpret_cast<u32x4*>(wbuf + buf * WB + tile_swz(c >> 3, c & 7)) = rb[SET][i];
     }
   };
   auto load_ds = [&](int cb) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < BCH; ++i) {
       const int c = tid + i * NT;
-      rds[i] = *reinterpret_cast<const s2u4*>(wds + (size_t)(n0 + (c >> 3)) * CIN + cb * KB + (c & 7) * CPR);
+      rds[i] = *reinterpret_cast<const u32x4*>(wds + (size_t)(n0 + (c >> 3)) * CIN + cb * KB + (c & 7) * CPR);
     }
   };
   auto store_ds = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < BCH; ++i) {
       const int c = tid + i * NT;
-      *reinterpret_cast<s2u4*>(dsbuf + s2swz(c >> 3, c & 7)) = rds[i];
+      *reinterpret_cast<u32x4*>(dsbuf + tile_swz(c >> 3, c & 7)) = rds[i];
     }
   };
 
   // lane -> output pixel and its patch position for tap (0,0)
-  const int o = s2frag_off(r16);
+  const int o = frag_pixel(r16);
   int ppix[TM];
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
@@ -199,13 +164,13 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
     }
 
   load_patch(0);
-  load_w(0, sc<0>{});
+  load_w(0, int_c<0>{});
   load_ds(0);
   store_patch();
-  store_w(0, sc<0>{});
+  store_w(0, int_c<0>{});
   store_ds();
-  load_w(1, sc<1>{});
-  load_w(2, sc<2>{});
+  load_w(1, int_c<1>{});
+  load_w(2, int_c<2>{});
   __syncthreads();
 
   auto step = [&](int cb, auto tapc) __attribute__((always_inline)) {
@@ -214,23 +179,23 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
     // stride-2 tap -> LDS position offset in the de-interleaved row
     constexpr int COL = KC == 0 ? 0 : (KC == 1 ? TW + 1 : 1);
     const int s = cb * 9 + TAP;
-    load_w(s + 3, sc<TAP % 3>{});
+    load_w(s + 3, int_c<TAP % 3>{});
     if constexpr (TAP == 0 && NCB > 1) load_patch(cb + 1 < NCB ? cb + 1 : NCB - 1);
     if constexpr (TAP == 1 && NCB > 1) load_ds(cb + 1 < NCB ? cb + 1 : NCB - 1);
     const char* wb = wbuf + (s & 1) * WB;
-    s2u4 fa[2][TN], fb[2][TM], fd[2][TN];
+    u32x4 fa[2][TN], fb[2][TM], fd[2][TN];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
-        fa[g][tn] = *reinterpret_cast<const s2u4*>(wb + s2swz(wn * WTN + tn * 16 + r16, g * 4 + q));
+        fa[g][tn] = *reinterpret_cast<const u32x4*>(wb + tile_swz(wn * WTN + tn * 16 + r16, g * 4 + q));
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
-        fb[g][tm] = *reinterpret_cast<const s2u4*>(patch + s2swz(ppix[tm] + KR * PW + COL, g * 4 + q));
+        fb[g][tm] = *reinterpret_cast<const u32x4*>(patch + tile_swz(ppix[tm] + KR * PW + COL, g * 4 + q));
       if constexpr (TAP == 4) {
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn)
-          fd[g][tn] = *reinterpret_cast<const s2u4*>(dsbuf + s2swz(wn * WTN + tn * 16 + r16, g * 4 + q));
+          fd[g][tn] = *reinterpret_cast<const u32x4*>(dsbuf + tile_swz(wn * WTN + tn * 16 + r16, g * 4 + q));
       }
     }
 #pragma unroll
@@ -239,10 +204,10 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
       for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn) {
-          s2mma<T>(acc[tm][tn], fa[g][tn], fb[g][tm]);
-          if constexpr (TAP == 4) s2mma<T>(accd[tm][tn], fd[g][tn], fb[g][tm]);  // centre tap = 1x1 s2 input
+          mfma16<T>(acc[tm][tn], fa[g][tn], fb[g][tm]);
+          if constexpr (TAP == 4) mfma16<T>(accd[tm][tn], fd[g][tn], fb[g][tm]);  // centre tap = 1x1 s2 input
         }
-    store_w((s + 1) & 1, sc<(TAP + 1) % 3>{});
+    store_w((s + 1) & 1, int_c<(TAP + 1) % 3>{});
     if constexpr (NCB > 1 && TAP == 8) {
       __syncthreads();  // every wave is done with the patch and the ds tile
       if (cb + 1 < NCB) {
@@ -253,15 +218,15 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3s2_ds(ConvS2Args a) {
     __syncthreads();
   };
   for (int cb = 0; cb < NCB; ++cb) {
-    step(cb, sc<0>{});
-    step(cb, sc<1>{});
-    step(cb, sc<2>{});
-    step(cb, sc<3>{});
-    step(cb, sc<4>{});
-    step(cb, sc<5>{});
-    step(cb, sc<6>{});
-    step(cb, sc<7>{});
-    step(cb, sc<8>{});
+    step(cb, int_c<0>{});
+    step(cb, int_c<1>{});
+    step(cb, int_c<2>{});
+    step(cb, int_c<3>{});
+    step(cb, int_c<4>{});
+    step(cb, int_c<5>{});
+    step(cb, int_c<6>{});
+    step(cb, int_c<7>{});
+    step(cb, int_c<8>{});
     if constexpr (BLOCKED) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)

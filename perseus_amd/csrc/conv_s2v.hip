@@ -30,21 +30,16 @@
 // consecutive positions; 144 bytes per position (conv_c64v.hip's 8 data chunks + 1 pad chunk,
 // the chunk of input channels 32 h + 8 q .. + 7 at 2 q + h): one VGPR plus ds_read immediates
 // addresses every fragment of the loop, and the ds_read_b128 lane groups are conflict-free
-// (conv_c64v.hip: with the xfrag pixel order a group's q = 0 lanes hit the even 16-byte bank
+// (conv_c64v.hip: with the frag_pixel pixel order a group's q = 0 lanes hit the even 16-byte bank
 // quads, its q = 1 lanes the odd ones).
 //
 // Sum order (bit-identity): each conv accumulator adds its MFMAs tap by tap in conv_s2w.h's
 // order (taps 3 4 5, 0 1 2, 6 7 8; the two 32-channel halves of each tap in order), the
 // downsample's its two halves, and the epilogue is conv_s2w.h's, so the outputs are bit for
 // bit those of the round-5 kernel (variant 6:40).
-#include "conv_gx.h"
+#include "conv.h"
 
 namespace pa {
-
-// group g of a tile's K loop: conv_s2w.h's tap order [3 4 5 0 1 2 6 7 8][g / 2], half g & 1
-__host__ __device__ constexpr int s2v_tap(int g) {
-  return (g >> 1) < 3 ? 3 + (g >> 1) : ((g >> 1) < 6 ? (g >> 1) - 3 : (g >> 1));
-}
 
 template <int TH>
 struct S2v {
@@ -95,7 +90,7 @@ __global__ __launch_bounds__(TH * 128, 2) void conv3x3s2_v(ConvS2Args a, int nti
 
   const unsigned abytes =
       (unsigned)((size_t)a.B * Hin * Win * 128 < 0x7fffffffu ? (size_t)a.B * Hin * Win * 128 : 0x7fffffffu);
-  const s2w_u4 rsrc = s2w_rsrc(in, abytes);
+  const u32x4 rsrc = s2w_rsrc(in, abytes);
   struct Org {
     int img, h0, x0;  // input row / column of patch position (0, 0): 2 th0 - 1, 2 tw0 - 1
     bool on;
@@ -134,7 +129,7 @@ __global__ __launch_bounds__(TH * 128, 2) void conv3x3s2_v(ConvS2Args a, int nti
       dma_patch(i, o, buf);  // wave-uniform
   };
 
-  const int o = xfrag(r16);
+  const int o = frag_pixel(r16);
   // this lane's patch-read base: input row 4 wm (of the patch), position o, chunk position 2 q
   const unsigned rbase =
       (unsigned)(size_t)(__attribute__((address_space(3))) char*)patch + (unsigned)((4 * wm * PW + o) * PXB + q * 32);
@@ -152,11 +147,11 @@ __global__ __launch_bounds__(TH * 128, 2) void conv3x3s2_v(ConvS2Args a, int nti
 #pragma unroll
     for (int i = 0; i < PDW; ++i) dma_one(i, o0, 0);
   }
-  xu4 wr[18][TN], wd[2][TN];
+  u32x4 wr[18][TN], wd[2][TN];
   {
-    const xu4* __restrict__ wf = reinterpret_cast<const xu4*>(a.wfrag) + (size_t)wn * 20 * TN * 64 + lane;
-    gx_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
-      constexpr int Gi = decltype(gc)::value, TAP = s2v_tap(Gi), K = 2 * TAP + (Gi & 1);
+    const u32x4* __restrict__ wf = reinterpret_cast<const u32x4*>(a.wfrag) + (size_t)wn * 20 * TN * 64 + lane;
+    const_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
+      constexpr int Gi = decltype(gc)::value, TAP = vgpr_tap(Gi), K = 2 * TAP + (Gi & 1);
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn) wr[K][tn] = wf[(K * TN + tn) * 64];
       if constexpr (TAP == 4) {
@@ -201,18 +196,18 @@ __global__ __launch_bounds__(TH * 128, 2) void conv3x3s2_v(ConvS2Args a, int nti
       }
     const __attribute__((address_space(3))) char* pb =
         (const __attribute__((address_space(3))) char*)(size_t)(rbase + buf * PATCHB);
-    xu4 fb[2][TM];
+    u32x4 fb[2][TM];
     auto rd = [&](auto gc) __attribute__((always_inline)) {
-      constexpr int Gi = decltype(gc)::value, TAP = s2v_tap(Gi), HG = Gi & 1, S = Gi & 1;
+      constexpr int Gi = decltype(gc)::value, TAP = vgpr_tap(Gi), HG = Gi & 1, S = Gi & 1;
       constexpr int KH = TAP / 3, KW = TAP % 3;
       constexpr int POFF = KW == 0 ? 0 : (KW == 1 ? TW + 1 : 1);
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
-        fb[S][tm] = *reinterpret_cast<const __attribute__((address_space(3))) xu4*>(
+        fb[S][tm] = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(
             pb + ((2 * tm + KH) * PW + POFF) * PXB + HG * 16);
     };
     auto mm = [&](auto gc) __attribute__((always_inline)) {
-      constexpr int Gi = decltype(gc)::value, TAP = s2v_tap(Gi), HG = Gi & 1, S = Gi & 1;
+      constexpr int Gi = decltype(gc)::value, TAP = vgpr_tap(Gi), HG = Gi & 1, S = Gi & 1;
       constexpr int K = 2 * TAP + HG;
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
@@ -229,10 +224,10 @@ __global__ __launch_bounds__(TH * 128, 2) void conv3x3s2_v(ConvS2Args a, int nti
                                                                   __builtin_bit_cast(half8, fb[S][tm]), accd[tm][tn], 0, 0, 0);
       }
     };
-    rd(xic<0>{});
-    gx_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
+    rd(int_c<0>{});
+    const_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
       constexpr int Gi = decltype(gc)::value;
-      if constexpr (Gi + 1 < 18) rd(xic<Gi + 1>{});
+      if constexpr (Gi + 1 < 18) rd(int_c<Gi + 1>{});
       __builtin_amdgcn_sched_barrier(0);  // next group's reads ahead of this group's MFMAs
       if constexpr (Gi < PDW) {  // next tile's patch, one DMA per group
         __builtin_amdgcn_sched_barrier(0);
@@ -255,7 +250,7 @@ __global__ __launch_bounds__(TH * 128, 2) void conv3x3s2_v(ConvS2Args a, int nti
     if constexpr (DBG == 4) trace_stamp(a.trace, 3 + 4 * t);
 
     // epilogue (conv_s2w.h's): lane (q, r16) holds channels 32 wn + 8 q .. + 7 of pixel o of rows
-    // 2 wm + tm (conv_gx.h xperm): relu(conv + bias) -> out, downsample + bias2 -> out2
+    // 2 wm + tm (conv_tile.h cout_perm): relu(conv + bias) -> out, downsample + bias2 -> out2
     const f32x4* b4 = reinterpret_cast<const f32x4*>(bias_l + wn * 32 + q * 8);
     const f32x4 b0 = b4[0], b1 = b4[1], d0 = b4[32], d1 = b4[33];
 #pragma unroll

@@ -171,7 +171,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_w(ConvS2Args a, int xg
     // K loop
     int ln = lane;
     asm volatile("" : "+v"(ln));
-    const s2w_u4 rs = s2w_rsrc(in + (size_t)img * Hin * Win * XS * CIN, (unsigned)(Hin * Win * XS * CIN * 2));
+    const u32x4 rs = s2w_rsrc(in + (size_t)img * Hin * Win * XS * CIN, (unsigned)(Hin * Win * XS * CIN * 2));
 #pragma unroll
     for (int i = 0; i < npc; ++i) {
       const int c = (i * NW + wid) * 64 + ln;
@@ -186,15 +186,15 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_w(ConvS2Args a, int xg
       s2w_dma16(rs, vo, patch + base * 128 + (i * NW + wid) * 1024);
     }
   };
-  // weights: ring row co holds output channel n0 + xperm(co) (16-byte epilogue)
+  // weights: ring row co holds output channel n0 + cout_perm(co) (16-byte epilogue)
   const _Float16* wsrc[WDMA];
   const _Float16* dsrc[WDMA];
 #pragma unroll
   for (int i = 0; i < WDMA; ++i) {
     const int c = (i * NW + wid) * 64 + lane;
     const int co = c >> 3, lc = (c & 7) ^ ((co >> 1) & 7);
-    wsrc[i] = w + (size_t)(n0 + xperm(co)) * (9 * XS * CIN) + lc * 8;
-    dsrc[i] = wds + (size_t)(n0 + xperm(co)) * XS * CIN + lc * 8;
+    wsrc[i] = w + (size_t)(n0 + cout_perm(co)) * (9 * XS * CIN) + lc * 8;
+    dsrc[i] = wds + (size_t)(n0 + cout_perm(co)) * XS * CIN + lc * 8;
   }
   auto dma_w = [&](int s) __attribute__((always_inline)) {
     const int t = s % 10, vb = (s / 10) % NVB, tap = s2w_tap(t);
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_w(ConvS2Args a, int xg
     }
   };
 
-  const int o = xfrag(r16);
+  const int o = frag_pixel(r16);
   int ppix[TM];  // LDS position of (row y of its region, column position of kw = 0) for this lane's pixel
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
@@ -289,8 +289,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_w(ConvS2Args a, int xg
     }
   };
 
-  const int abase[2] = {xswz(r16, q), xswz(r16, 4 + q)};
-  xu4 fa[2][TN], fb[2][TM];
+  const int abase[2] = {tile_swz(r16, q), tile_swz(r16, 4 + q)};
+  u32x4 fa[2][TN], fb[2][TM];
   auto read_frags = [&](auto kc) __attribute__((always_inline)) {
     constexpr int K = decltype(kc)::value;
     constexpr int S = K >> 1, HG = K & 1, T = S % 10;
@@ -301,9 +301,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_w(ConvS2Args a, int xg
     // tn / wn (multiples of 16 rows), so every read is one per-lane base + an immediate offset
     const char* wb = wring + (S % NSLOT) * WB + wn * WTN * 128 + abase[HG];
 #pragma unroll
-    for (int tn = 0; tn < TN; ++tn) fa[HG][tn] = *reinterpret_cast<const xu4*>(wb + tn * 16 * 128);
+    for (int tn = 0; tn < TN; ++tn) fa[HG][tn] = *reinterpret_cast<const u32x4*>(wb + tn * 16 * 128);
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm) fb[HG][tm] = *reinterpret_cast<const xu4*>(patch + xswz(ppix[tm] + TOFF, HG * 4 + q));
+    for (int tm = 0; tm < TM; ++tm) fb[HG][tm] = *reinterpret_cast<const u32x4*>(patch + tile_swz(ppix[tm] + TOFF, HG * 4 + q));
   };
   auto mfma = [&](auto hc, auto dsc) __attribute__((always_inline)) {
     constexpr int HG = decltype(hc)::value;
@@ -317,8 +317,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_w(ConvS2Args a, int xg
                                                    __builtin_bit_cast(half8, fb[HG][tm]), d, 0, 0, 0);
       }
   };
-  read_frags(xic<0>{});
-  gx_for<0, NSTEPS>([&](auto sc) __attribute__((always_inline)) {
+  read_frags(int_c<0>{});
+  const_for<0, NSTEPS>([&](auto sc) __attribute__((always_inline)) {
     constexpr int S = decltype(sc)::value;
     constexpr int U = S / 10, T = S % 10;
     using DS = std::integral_constant<bool, T == 3>;
@@ -334,11 +334,11 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_w(ConvS2Args a, int xg
         }
       __builtin_amdgcn_sched_barrier(0);
     }
-    read_frags(xic<2 * S + 1>{});
+    read_frags(int_c<2 * S + 1>{});
     __builtin_amdgcn_s_setprio(1);
-    mfma(xic<0>{}, DS{});
+    mfma(int_c<0>{}, DS{});
     __builtin_amdgcn_s_setprio(0);
-    if constexpr (S + 1 < NSTEPS) read_frags(xic<2 * S + 2>{});
+    if constexpr (S + 1 < NSTEPS) read_frags(int_c<2 * S + 2>{});
     // DMAs after this step's LDS reads (see xdma16); order = S2wPlan's
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (S + PD < NSTEPS) dma_w(S + PD);
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_w(ConvS2Args a, int xg
       dma_region(U + 1, std::true_type{});  // the next unit's even rows (this unit's are done)
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
-    mfma(xic<1>{}, DS{});
+    mfma(int_c<1>{}, DS{});
     __builtin_amdgcn_s_setprio(0);
     if constexpr (S + 2 < NSTEPS) {
       // the next step reads the fragments of step S + 2's first half at its end

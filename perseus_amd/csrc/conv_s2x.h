@@ -124,13 +124,13 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_x(ConvS2Args a, int xg
 
   // patch DMA: LDS slot c = (i * NW + wid) * 64 + lane holds position p = c >> 3,
   // logical chunk (c & 7) ^ swizzle(p); block blk = tile j's virtual block vb.  Through a
-  // buffer resource over this image (conv_gx.h s2w_dma16): the per-lane byte offset of a tile
+  // buffer resource over this image (conv_tile.h s2w_dma16): the per-lane byte offset of a tile
   // is computed once (tile_off), a block adds a constant, and halo / padding lanes carry an
   // out-of-range offset (S2W_OOB + block offset stays out of range) and read zeros.  (The
   // pointer form recomputed the tile, selected a 64-bit pointer against a zero line whose
   // address came through the GOT behind s_waitcnt lgkmcnt(0) -- draining the fragment reads --
   // at every DMA of the K loop.)
-  const s2w_u4 prs = s2w_rsrc((const _Float16*)a.in + (size_t)img * Hin * Win * kin,
+  const u32x4 prs = s2w_rsrc((const _Float16*)a.in + (size_t)img * Hin * Win * kin,
                               (unsigned)((size_t)Hin * Win * kin * 2));
   auto tile_off = [&](int j, unsigned (&po)[PDMA]) __attribute__((always_inline)) {
     int th0, tw0;
@@ -159,15 +159,15 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_x(ConvS2Args a, int xg
 #pragma unroll
     for (int i = 0; i < PDMA; ++i) s2w_dma16(prs, poff[i] + bo, patch + buf * PATCHB + (i * NW + wid) * 1024);
   };
-  // weights: ring row co holds output channel n0 + xperm(co) (16-byte epilogue)
+  // weights: ring row co holds output channel n0 + cout_perm(co) (16-byte epilogue)
   const _Float16* wsrc[WDMA];
   const _Float16* dsrc[WDMA];
 #pragma unroll
   for (int i = 0; i < WDMA; ++i) {
     const int c = (i * NW + wid) * 64 + lane;
     const int co = c >> 3, lc = (c & 7) ^ ((co >> 1) & 7);
-    wsrc[i] = w + (size_t)(n0 + xperm(co)) * (9 * kin) + lc * 8;
-    dsrc[i] = wds + (size_t)(n0 + xperm(co)) * kin + lc * 8;
+    wsrc[i] = w + (size_t)(n0 + cout_perm(co)) * (9 * kin) + lc * 8;
+    dsrc[i] = wds + (size_t)(n0 + cout_perm(co)) * kin + lc * 8;
   }
   auto dma_w = [&](int s) __attribute__((always_inline)) {
     const int vb = (s % SPT) / SPB, t = s % SPB;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_x(ConvS2Args a, int xg
     }
   };
 
-  const int o = xfrag(r16);
+  const int o = frag_pixel(r16);
   int ppix[TM];  // LDS position of tap (0, 0) for this lane's pixel of fragment tm
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_x(ConvS2Args a, int xg
     }
   };
 
-  xu4 fa[2][TN], fb[2][TM];
+  u32x4 fa[2][TN], fb[2][TM];
   auto read_frags = [&](auto kc) __attribute__((always_inline)) {
     constexpr int K = decltype(kc)::value;
     constexpr int S = K >> 1, HG = K & 1, CB = S / SPB, T = S % SPB;
@@ -269,9 +269,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_x(ConvS2Args a, int xg
     const char* wb = wring + (S % NSLOT) * WB;
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn)
-      fa[HG][tn] = *reinterpret_cast<const xu4*>(wb + xswz(wn * WTN + tn * 16 + r16, HG * 4 + q));
+      fa[HG][tn] = *reinterpret_cast<const u32x4*>(wb + tile_swz(wn * WTN + tn * 16 + r16, HG * 4 + q));
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm) fb[HG][tm] = *reinterpret_cast<const xu4*>(pb + xswz(ppix[tm] + TOFF, HG * 4 + q));
+    for (int tm = 0; tm < TM; ++tm) fb[HG][tm] = *reinterpret_cast<const u32x4*>(pb + tile_swz(ppix[tm] + TOFF, HG * 4 + q));
   };
   auto mfma = [&](auto hc, auto dsc) __attribute__((always_inline)) {
     constexpr int HG = decltype(hc)::value;
@@ -285,8 +285,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_x(ConvS2Args a, int xg
                                                    __builtin_bit_cast(half8, fb[HG][tm]), d, 0, 0, 0);
       }
   };
-  read_frags(xic<0>{});
-  gx_for<0, NSTEPS>([&](auto sc) __attribute__((always_inline)) {
+  read_frags(int_c<0>{});
+  const_for<0, NSTEPS>([&](auto sc) __attribute__((always_inline)) {
     constexpr int S = decltype(sc)::value;
     constexpr int CB = S / SPB;
     using DS = std::integral_constant<bool, S % SPB == 9>;
@@ -302,11 +302,11 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_x(ConvS2Args a, int xg
         }
       __builtin_amdgcn_sched_barrier(0);
     }
-    read_frags(xic<2 * S + 1>{});
+    read_frags(int_c<2 * S + 1>{});
     __builtin_amdgcn_s_setprio(1);
-    mfma(xic<0>{}, DS{});
+    mfma(int_c<0>{}, DS{});
     __builtin_amdgcn_s_setprio(0);
-    if constexpr (S + 1 < NSTEPS) read_frags(xic<2 * S + 2>{});
+    if constexpr (S + 1 < NSTEPS) read_frags(int_c<2 * S + 2>{});
     // DMAs after this step's LDS reads (see xdma16); order = GxPlan's
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (S + PD < NSTEPS) dma_w(S + PD);
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3x3s2_x(ConvS2Args a, int xg
     }
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
-    mfma(xic<1>{}, DS{});
+    mfma(int_c<1>{}, DS{});
     __builtin_amdgcn_s_setprio(0);
     if constexpr ((S + 1) % G == 0 && S + 2 < NSTEPS) {
       constexpr int V = S + G + 1 < NSTEPS ? S + G + 1 : NSTEPS - 1;

@@ -18,13 +18,9 @@
 //
 // Sum order: another order than conv_s2w.h's X3 form (one accumulator over all taps and blocks,
 // plane by plane): within f32 rounding of it, far inside the parity mode's 1e-3 px.
-#include "conv_gx.h"
+#include "conv.h"
 
 namespace pa {
-
-__host__ __device__ constexpr int x3k_tap(int g) {  // group g: tap [3 4 5 0 1 2 6 7 8][g / 2], half g & 1
-  return (g >> 1) < 3 ? 3 + (g >> 1) : ((g >> 1) < 6 ? (g >> 1) - 3 : (g >> 1));
-}
 
 struct X3s2k {
   static constexpr int NB = 2, WC = 4, TW = 16, PW = 2 * TW + 1, NP = 3 * PW;  // 99 positions per block
@@ -38,12 +34,6 @@ struct X3s2k {
   static_assert(SMEM + 4 * 64 * 4 <= 160 * 1024, "LDS");
   static_assert(PDW <= 18 - 2, "patch DMAs within the K loop");
 };
-
-__device__ __forceinline__ void x3k_store8(void* base, unsigned off, half4 v) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000);
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, (int)off, 0, 16);
-}
 
 // DBG = 4: s_memrealtime stamps into a.trace (0 start, 1 first patch landed; tile t < 20: 2 + 3 t
 // start, 3 + 3 t K loop done, 4 + 3 t hand-over barrier passed; 63 end)
@@ -88,7 +78,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_k3(ConvS2Args a, int ntiles,
   const unsigned abytes = (unsigned)((size_t)a.B * Hin * Win * XS * CIN * 2 < 0x7fffffffu
                                          ? (size_t)a.B * Hin * Win * XS * CIN * 2
                                          : 0x7fffffffu);
-  const s2w_u4 rsrc = s2w_rsrc(a.in, abytes);
+  const u32x4 rsrc = s2w_rsrc(a.in, abytes);
   struct Org {
     int img, h0;
     bool on;
@@ -123,7 +113,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_k3(ConvS2Args a, int ntiles,
     }
   };
 
-  const int o = xfrag(r16);
+  const int o = frag_pixel(r16);
   // this lane's patch-read base: its block's region, position o of patch row 0, chunk position 2 q
   const unsigned rbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)patch +
                          (unsigned)(wb * NRC * 16 + o * PXB + q * 32);
@@ -143,12 +133,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_k3(ConvS2Args a, int ntiles,
 #pragma unroll
     for (int i = 0; i < PDW; ++i) dma_one(i, o0, 0);
   }
-  xu4 wh[18], wl[18], dh[2], dl[2];
+  u32x4 wh[18], wl[18], dh[2], dl[2];
   {
-    const xu4* __restrict__ wf =
-        reinterpret_cast<const xu4*>(a.wfrag) + (size_t)((h * NB + wb) * WC + wc) * 20 * 2 * 64 + lane;
-    gx_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
-      constexpr int Gi = decltype(gc)::value, TAP = x3k_tap(Gi), K = 2 * TAP + (Gi & 1);
+    const u32x4* __restrict__ wf =
+        reinterpret_cast<const u32x4*>(a.wfrag) + (size_t)((h * NB + wb) * WC + wc) * 20 * 2 * 64 + lane;
+    const_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
+      constexpr int Gi = decltype(gc)::value, TAP = vgpr_tap(Gi), K = 2 * TAP + (Gi & 1);
       wh[K] = wf[(K * 2 + 0) * 64];
       wl[K] = wf[(K * 2 + 1) * 64];
       if constexpr (TAP == 4) {
@@ -179,17 +169,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_k3(ConvS2Args a, int ntiles,
     f32x4 ahh = {0.f, 0.f, 0.f, 0.f}, alh = ahh, ahl = ahh, dhh = ahh, dlh = ahh, dhl = ahh;
     const __attribute__((address_space(3))) char* pb =
         (const __attribute__((address_space(3))) char*)(size_t)(rbase + buf * PATCHB);
-    xu4 xh[RA], xl[RA];
+    u32x4 xh[RA], xl[RA];
     auto rd = [&](auto gc) __attribute__((always_inline)) {
-      constexpr int Gi = decltype(gc)::value, TAP = x3k_tap(Gi), HG = Gi & 1, S = Gi % RA;
+      constexpr int Gi = decltype(gc)::value, TAP = vgpr_tap(Gi), HG = Gi & 1, S = Gi % RA;
       constexpr int KH = TAP / 3, KW = TAP % 3;
       constexpr int POFF = KW == 0 ? 0 : (KW == 1 ? TW + 1 : 1);
-      const auto* p = reinterpret_cast<const __attribute__((address_space(3))) xu4*>(pb + (KH * PW + POFF) * PXB + HG * 16);
+      const auto* p = reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(pb + (KH * PW + POFF) * PXB + HG * 16);
       xh[S] = p[0];
       xl[S] = p[8];  // + 128 bytes: the lo plane
     };
     auto mm = [&](auto gc) __attribute__((always_inline)) {
-      constexpr int Gi = decltype(gc)::value, TAP = x3k_tap(Gi), HG = Gi & 1, S = Gi % RA;
+      constexpr int Gi = decltype(gc)::value, TAP = vgpr_tap(Gi), HG = Gi & 1, S = Gi % RA;
       constexpr int K = 2 * TAP + HG;
       const half8 h = __builtin_bit_cast(half8, xh[S]), l = __builtin_bit_cast(half8, xl[S]);
       ahh = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, wh[K]), h, ahh, 0, 0, 0);
@@ -201,11 +191,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_k3(ConvS2Args a, int ntiles,
         dhl = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, dh[HG]), l, dhl, 0, 0, 0);
       }
     };
-    rd(xic<0>{});
-    rd(xic<1>{});
-    gx_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
+    rd(int_c<0>{});
+    rd(int_c<1>{});
+    const_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
       constexpr int Gi = decltype(gc)::value;
-      if constexpr (Gi + 2 < 18) rd(xic<Gi + 2>{});
+      if constexpr (Gi + 2 < 18) rd(int_c<Gi + 2>{});
       __builtin_amdgcn_sched_barrier(0);  // reads two groups ahead of this group's MFMAs
       if constexpr (Gi < PDW) {           // next tile's patch, one DMA per group
         __builtin_amdgcn_sched_barrier(0);
@@ -213,7 +203,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_k3(ConvS2Args a, int ntiles,
         __builtin_amdgcn_sched_barrier(0);
       } else if constexpr (DS && Gi < PDW + 2) {  // the previous tile's outputs
         __builtin_amdgcn_sched_barrier(0);
-        if (t > 0) x3k_store8(dsto, Gi == PDW ? pob : pob + Cout * 2, Gi == PDW ? phi : plo);
+        if (t > 0) store_half4(dsto, Gi == PDW ? pob : pob + Cout * 2, Gi == PDW ? phi : plo);
         __builtin_amdgcn_sched_barrier(0);
       }
       mm(gc);
@@ -260,8 +250,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_k3(ConvS2Args a, int ntiles,
       plo = lo;
       pob = ob;
     } else {
-      x3k_store8(dsto, ob, hi);
-      x3k_store8(dsto, ob + Cout * 2, lo);
+      store_half4(dsto, ob, hi);
+      store_half4(dsto, ob + Cout * 2, lo);
     }
     j = jn;
     jn = j + nslots;
@@ -271,8 +261,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_k3(ConvS2Args a, int ntiles,
   for (int t = 1; j < ntiles; ++t) run_tile(std::false_type{}, t);  // (run_tile advances j)
   if constexpr (DS) {  // the last tile's outputs
     if (any) {
-      x3k_store8(dsto, pob, phi);
-      x3k_store8(dsto, pob + Cout * 2, plo);
+      store_half4(dsto, pob, phi);
+      store_half4(dsto, pob + Cout * 2, plo);
     }
   }
   if constexpr (DBG == 4) {

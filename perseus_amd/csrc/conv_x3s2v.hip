@@ -25,13 +25,9 @@
 // than conv_s2w.h's X3 form (all taps of x_hi w_hi, then of x_hi w_lo, then of x_lo w_hi), so
 // not bit-identical to it (both well inside the parity mode's 1e-3 px).  Epilogue: conv_s2w.h
 // X3's (exact unscale by 2^-e, bias, ReLU, (hi, lo) split), 8-byte stores per plane.
-#include "conv_gx.h"
+#include "conv.h"
 
 namespace pa {
-
-__host__ __device__ constexpr int x3v_tap(int g) {  // group g: tap [3 4 5 0 1 2 6 7 8][g / 2], half g & 1
-  return (g >> 1) < 3 ? 3 + (g >> 1) : ((g >> 1) < 6 ? (g >> 1) - 3 : (g >> 1));
-}
 
 struct X3s2v {
   static constexpr int TH = 2, TW = 16, PW = 2 * TW + 1, NP = (2 * TH + 1) * PW;  // 165 positions
@@ -44,12 +40,6 @@ struct X3s2v {
   static constexpr int SMEM = 2 * PATCHB + STG;
   static_assert(SMEM + 512 * 4 <= 160 * 1024, "LDS");
 };
-
-__device__ __forceinline__ void x3_store8(void* base, unsigned off, half4 v) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000);
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, (int)off, 0, 16);
-}
 
 // DBG = 4: s_memrealtime stamps into a.trace (0 start, 1 first patch landed; tile t < 15: 2 + 4 t
 // start, 3 + 4 t K loop done and next patch landed, 4 + 4 t stores issued; 63 end)
@@ -81,7 +71,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_v3(ConvS2Args a, int ntiles)
   const unsigned abytes = (unsigned)((size_t)a.B * Hin * Win * XS * CIN * 2 < 0x7fffffffu
                                          ? (size_t)a.B * Hin * Win * XS * CIN * 2
                                          : 0x7fffffffu);
-  const s2w_u4 rsrc = s2w_rsrc(a.in, abytes);
+  const u32x4 rsrc = s2w_rsrc(a.in, abytes);
   struct Org {
     int img, h0, x0;
     bool on;
@@ -116,7 +106,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_v3(ConvS2Args a, int ntiles)
     }
   };
 
-  const int o = xfrag(r16);
+  const int o = frag_pixel(r16);
   // this lane's patch-read base: position o of patch row 0, chunk position 2 q (hi plane)
   const unsigned rbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)patch + (unsigned)(o * PXB + q * 32);
   if (tid < 128) {
@@ -136,11 +126,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_v3(ConvS2Args a, int ntiles)
 #pragma unroll
     for (int i = 0; i < PDW; ++i) dma_one(i, o0, 0);
   }
-  xu4 wh[18], wl[18], dh[2], dl[2];
+  u32x4 wh[18], wl[18], dh[2], dl[2];
   {
-    const xu4* __restrict__ wf = reinterpret_cast<const xu4*>(a.wfrag) + (size_t)wn * 20 * 2 * 64 + lane;
-    gx_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
-      constexpr int Gi = decltype(gc)::value, TAP = x3v_tap(Gi), K = 2 * TAP + (Gi & 1);
+    const u32x4* __restrict__ wf = reinterpret_cast<const u32x4*>(a.wfrag) + (size_t)wn * 20 * 2 * 64 + lane;
+    const_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
+      constexpr int Gi = decltype(gc)::value, TAP = vgpr_tap(Gi), K = 2 * TAP + (Gi & 1);
       wh[K] = wf[(K * 2 + 0) * 64];
       wl[K] = wf[(K * 2 + 1) * 64];
       if constexpr (TAP == 4) {
@@ -164,7 +154,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_v3(ConvS2Args a, int ntiles)
   auto store_staged = [&](int sidx) __attribute__((always_inline)) {
     const int tm = sidx >> 2, kind = (sidx >> 1) & 1, pl = sidx & 1;
     const half4 v = *reinterpret_cast<const half4*>(stg + sidx * 512);
-    x3_store8(kind ? out2 : out, pend_base + olane + (unsigned)(tm * W * XS * Cout * 2 + pl * Cout * 2), v);
+    store_half4(kind ? out2 : out, pend_base + olane + (unsigned)(tm * W * XS * Cout * 2 + pl * Cout * 2), v);
   };
   // one tile; the first is its own copy of the body (FIRST): there the compiler's vmcnt waits hold
   // each group's MFMAs until that group's weight fragments have landed
@@ -187,23 +177,23 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_v3(ConvS2Args a, int ntiles)
     }
     const __attribute__((address_space(3))) char* pb =
         (const __attribute__((address_space(3))) char*)(size_t)(rbase + buf * PATCHB);
-    xu4 xh[2][TM], xl[2][TM];
+    u32x4 xh[2][TM], xl[2][TM];
     auto rd = [&](auto gc) __attribute__((always_inline)) {
-      constexpr int Gi = decltype(gc)::value, TAP = x3v_tap(Gi), HG = Gi & 1, S = Gi & 1;
+      constexpr int Gi = decltype(gc)::value, TAP = vgpr_tap(Gi), HG = Gi & 1, S = Gi & 1;
       constexpr int KH = TAP / 3, KW = TAP % 3;
       constexpr int POFF = KW == 0 ? 0 : (KW == 1 ? TW + 1 : 1);
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm) {
-        const auto* p = reinterpret_cast<const __attribute__((address_space(3))) xu4*>(
+        const auto* p = reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(
             pb + ((2 * tm + KH) * PW + POFF) * PXB + HG * 16);
         xh[S][tm] = p[0];
         xl[S][tm] = p[8];  // + 128 bytes: the lo plane
       }
     };
     auto mm = [&](auto gc) __attribute__((always_inline)) {
-      constexpr int Gi = decltype(gc)::value, TAP = x3v_tap(Gi), HG = Gi & 1, S = Gi & 1;
+      constexpr int Gi = decltype(gc)::value, TAP = vgpr_tap(Gi), HG = Gi & 1, S = Gi & 1;
       constexpr int K = 2 * TAP + HG;
-      auto m3 = [&](f32x4(&ac)[TM], const xu4& h, const xu4& l) __attribute__((always_inline)) {
+      auto m3 = [&](f32x4(&ac)[TM], const u32x4& h, const u32x4& l) __attribute__((always_inline)) {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
           ac[tm] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, h), __builtin_bit_cast(half8, xh[S][tm]),
@@ -220,10 +210,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_v3(ConvS2Args a, int ntiles)
       m3(acc, wh[K], wl[K]);
       if constexpr (TAP == 4) m3(accd, dh[HG], dl[HG]);  // the downsample reads tap 4's pixels
     };
-    rd(xic<0>{});
-    gx_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
+    rd(int_c<0>{});
+    const_for<0, 18>([&](auto gc) __attribute__((always_inline)) {
       constexpr int Gi = decltype(gc)::value;
-      if constexpr (Gi + 1 < 18) rd(xic<Gi + 1>{});
+      if constexpr (Gi + 1 < 18) rd(int_c<Gi + 1>{});
       __builtin_amdgcn_sched_barrier(0);  // next group's reads ahead of this group's MFMAs
       if constexpr (Gi < PDW) {           // next tile's patch, one DMA per group
         __builtin_amdgcn_sched_barrier(0);
@@ -275,10 +265,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_v3(ConvS2Args a, int ntiles)
         *reinterpret_cast<half4*>(stg + (tm * 4 + 3) * 512) = l2;
       } else {
         const unsigned ob = (unsigned)((((img * H + th0 + tm) * W + tw0 + o) * XS * Cout + ch) * 2);
-        x3_store8(out, ob, h1);
-        x3_store8(out, ob + Cout * 2, l1);
-        x3_store8(out2, ob, h2);
-        x3_store8(out2, ob + Cout * 2, l2);
+        store_half4(out, ob, h1);
+        store_half4(out, ob + Cout * 2, l1);
+        store_half4(out2, ob, h2);
+        store_half4(out2, ob + Cout * 2, l2);
       }
     }
     if constexpr (DS) pend_base = (unsigned)((((img * H + th0) * W + tw0) * XS * Cout) * 2);

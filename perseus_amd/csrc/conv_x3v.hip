@@ -18,7 +18,7 @@
 // DMA'd one tile ahead with the patch so the epilogue needs no barrier of its own; the weights
 // (147 KB) are staged through [patch 1 | residual 1] in two rounds of 5 and 4 taps; bias and scale
 // live in registers.
-#include "conv_gx.h"
+#include "conv.h"
 
 namespace pa {
 
@@ -38,10 +38,6 @@ static_assert(PJ == 48 && PJ % NWAVE == 0, "patch DMA split");
 static_assert(BSTR >= WR0 * 64 * WROW, "weight staging in patch 1 + residual 1");
 static_assert(2 * BSTR <= 160 * 1024, "LDS");
 }  // namespace x3v
-
-// weight row co (chunk c of 16) at LDS chunk c ^ (co & 15): a wave's 16 rows at one chunk hit 16
-// different bank quads
-__device__ __forceinline__ int x3v_wswz(int row, int chunk) { return row * 256 + ((chunk ^ (row & 15)) << 4); }
 
 // DS: a tile's 8 output half4 per lane are stored during the next tile's K loop (steps 6 .. 13, after
 // the patch DMAs) instead of at the tile's end (conv_s2v.hip's deferred stores).  Plain convs: held in
@@ -73,7 +69,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x3v(ConvArgs a, int ntiles) {
   };
 
   const unsigned abytes = (unsigned)((size_t)a.B * H * W * 256 < 0x7fffffffu ? (size_t)a.B * H * W * 256 : 0x7fffffffu);
-  const s2w_u4 rsrc = s2w_rsrc(in, abytes);
+  const u32x4 rsrc = s2w_rsrc(in, abytes);
   struct Org {
     int img, h0, x0;
     bool on;
@@ -106,7 +102,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x3v(ConvArgs a, int ntiles) {
   };
   // residual tile (hi | lo, 256 B per pixel) by DMA i: slot c -> tile pixel c >> 4 = 32 i + m
   // (m = 4 wid + lane / 16), chunk c & 15 stored as logical chunk (c & 15) ^ (pixel & 15)
-  const s2w_u4 rres = s2w_rsrc(a.res ? a.res : a.in, abytes);
+  const u32x4 rres = s2w_rsrc(a.res ? a.res : a.in, abytes);
   const int mres = 4 * wid + (lane >> 4);
   const unsigned rrel = (unsigned)((((mres >> 4) * W + (mres & 15)) * 128 + (((lane & 15) ^ (mres & 15)) * 8)) * 2);
   auto dma_res = [&](int i, int img, int th0, int tw0, int rb) __attribute__((always_inline)) {
@@ -114,7 +110,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x3v(ConvArgs a, int ntiles) {
     s2w_dma16(rres, tb + rrel, smem + rb * BSTR + PATCHB + (i * NWAVE + wid) * 1024);
   };
 
-  const int o = xfrag(r16);
+  const int o = frag_pixel(r16);
   const unsigned rbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)patch + (unsigned)((wm * 4 * PW + o) * PXB + q * 32);
   const int c0 = wn * 16 + q * 4;  // this lane's 4 consecutive output channels
   const f32x4 bias = *reinterpret_cast<const f32x4*>(a.bias + c0);
@@ -134,7 +130,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x3v(ConvArgs a, int ntiles) {
   // weights: row co of tap t = [hi 64 | lo 64] of output channel co (w + co * 1152 + t * 128), staged
   // by LDS-DMA in rounds of taps; fragment (K, h) of this wave = channel 16 wn + r16, tap K / 2,
   // input channels 32 (K & 1) + 8 q .. + 7 of plane h
-  xu4 whi[18], wlo[18];
+  u32x4 whi[18], wlo[18];
   auto stage = [&](auto t0c, auto t1c) __attribute__((always_inline)) {
     constexpr int T0 = decltype(t0c)::value, T1 = decltype(t1c)::value;
     // tap (64 rows x 256 B = 16 KB) = 16 wave-DMAs of 4 rows: 2 per wave
@@ -151,13 +147,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x3v(ConvArgs a, int ntiles) {
 #pragma unroll
     for (int k = 2 * T0; k < 2 * T1; ++k) {
       const int row = ((k >> 1) - T0) * 64 + wn * 16 + r16;
-      whi[k] = *reinterpret_cast<const xu4*>(wst + x3v_wswz(row, (k & 1) * 4 + q));
-      wlo[k] = *reinterpret_cast<const xu4*>(wst + x3v_wswz(row, 8 + (k & 1) * 4 + q));
+      whi[k] = *reinterpret_cast<const u32x4*>(wst + tile_swz256(row, (k & 1) * 4 + q));
+      wlo[k] = *reinterpret_cast<const u32x4*>(wst + tile_swz256(row, 8 + (k & 1) * 4 + q));
     }
     lds_barrier();
   };
-  stage(xic<0>{}, xic<WR0>{});
-  stage(xic<WR0>{}, xic<9>{});
+  stage(int_c<0>{}, int_c<WR0>{});
+  stage(int_c<WR0>{}, int_c<9>{});
 
   constexpr bool DSR = DS && (EPI & EPI_RES) && NDX >= TM;  // staged in the residual buffer
   constexpr int NDR = DS && !DSR && NDX < TM ? NDX : TM;    // rows deferred: TM - NDR .. TM - 1
@@ -185,14 +181,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x3v(ConvArgs a, int ntiles) {
     for (int i = 0; i < TM; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     const __attribute__((address_space(3))) char* pb =
         (const __attribute__((address_space(3))) char*)(size_t)(rbase + buf * BSTR);
-    xu4 fb[2][TM];
+    u32x4 fb[2][TM];
     // step K < 18: x_hi of group K; K >= 18: x_lo of group K - 18
     auto rd = [&](auto kc) __attribute__((always_inline)) {
       constexpr int K = decltype(kc)::value, G = K % 18, TAP = G >> 1, HG = G & 1, S = K & 1, LO = K >= 18;
       constexpr int TOFF = (TAP / 3) * PW + (TAP % 3);
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
-        fb[S][tm] = *reinterpret_cast<const __attribute__((address_space(3))) xu4*>(pb + (tm * PW + TOFF) * PXB + LO * 128 + HG * 16);
+        fb[S][tm] = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(pb + (tm * PW + TOFF) * PXB + LO * 128 + HG * 16);
     };
     auto mm = [&](auto kc) __attribute__((always_inline)) {
       constexpr int K = decltype(kc)::value, G = K % 18, S = K & 1;
@@ -212,10 +208,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x3v(ConvArgs a, int ntiles) {
                                                            acc[tm], 0, 0, 0);
       }
     };
-    rd(xic<0>{});
-    gx_for<0, 36>([&](auto kc) __attribute__((always_inline)) {
+    rd(int_c<0>{});
+    const_for<0, 36>([&](auto kc) __attribute__((always_inline)) {
       constexpr int K = decltype(kc)::value;
-      if constexpr (K + 1 < 36) rd(xic<K + 1>{});
+      if constexpr (K + 1 < 36) rd(int_c<K + 1>{});
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (K < PDW) {  // the next tile's patch
         __builtin_amdgcn_sched_barrier(0);

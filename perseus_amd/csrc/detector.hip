@@ -38,8 +38,30 @@ struct Block {
   int conv1, conv2, ds;  // indices into convs; ds = -1 when identity
 };
 
-// conv_gx.h xperm on the host (weight packing)
-static inline int xperm_host(int rho) { return (rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3); }
+// VGPR-order weight fragments of a stride-2 block entry (conv 3x3 s2 + 1x1 s2 downsample), as
+// conv_s2v.hip, conv_x3s2v.hip and conv_x3s2k.hip load them: [outer nouter][fragment 20][sub 2][lane
+// 64][8].  Lane 16 q + r16 of fragment k holds input channels 32 (k & 1) + 8 q + e of one output
+// channel, of tap k / 2 (k < 18) or of the downsample (k = 18, 19).  What differs between the three
+// layouts is `at(outer, sub, r16)`: the output channel, and the offset of its 64 input channels within
+// a tap's `krow` elements (the hi / lo plane, the 64-channel block).  w: [cout][9][krow], wds: [cout][krow].
+struct FragRow {
+  int co, off;
+};
+template <typename F>
+static std::vector<_Float16> pack_vgpr_frags(const _Float16* w, const _Float16* wds, int krow, int nouter, F at) {
+  std::vector<_Float16> hv((size_t)nouter * 20 * 2 * 64 * 8);
+  size_t i = 0;
+  for (int o = 0; o < nouter; ++o)
+    for (int k = 0; k < 20; ++k)
+      for (int sub = 0; sub < 2; ++sub)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int q = lane >> 4, r16 = lane & 15;
+          const FragRow r = at(o, sub, r16);
+          const _Float16* src = (k < 18 ? w + ((size_t)r.co * 9 + (k >> 1)) * krow : wds + (size_t)r.co * krow) + r.off;
+          for (int e = 0; e < 8; ++e) hv[i++] = src[32 * (k & 1) + 8 * q + e];
+        }
+  return hv;
+}
 
 }  // namespace pa
 
@@ -76,6 +98,14 @@ struct pa_detector {
 };
 
 namespace pa {
+
+// hipMalloc *dst for n elements and copy them in from the host
+template <typename T>
+static int upload(T** dst, const T* src, size_t n) {
+  PA_HIP(hipMalloc(dst, n * sizeof(T)));
+  PA_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+  return PA_OK;
+}
 
 // Parse + fold + pack.  Returns PA_OK or an error code.
 static int build(pa_detector* d, const float* blob, size_t nfloats) {
@@ -173,8 +203,6 @@ static int build(pa_detector* d, const float* blob, size_t nfloats) {
   if (pos != nfloats) return -2;
 
   // algorithmic FLOPs (2 x MAC; stem at its true K = 49*Cin)
-  const int hw_in[4] = {64, 64, 32, 16};
-  (void)hw_in;
   double fl = 2.0 * 128 * 128 * 64 * 49.0 * d->in_ch;
   int hw = 64;
   for (const Block& b : d->blocks) {
@@ -188,88 +216,41 @@ static int build(pa_detector* d, const float* blob, size_t nfloats) {
   fl += 2.0 * 512 * nout;
   d->flops_per_frame = fl;
 
-  PA_HIP(hipMalloc(&d->w16, h16.size() * sizeof(_Float16)));
-  PA_HIP(hipMalloc(&d->w32, h32.size() * sizeof(float)));
-  PA_HIP(hipMalloc(&d->bias, hb.size() * sizeof(float)));
-  PA_HIP(hipMalloc(&d->fcw, (size_t)nout * 512 * sizeof(float)));
-  PA_HIP(hipMalloc(&d->fcb, (size_t)nout * sizeof(float)));
-  PA_HIP(hipMemcpy(d->w16, h16.data(), h16.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-  PA_HIP(hipMemcpy(d->w32, h32.data(), h32.size() * sizeof(float), hipMemcpyHostToDevice));
-  PA_HIP(hipMemcpy(d->bias, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice));
-  PA_HIP(hipMemcpy(d->fcw, fw, (size_t)nout * 512 * sizeof(float), hipMemcpyHostToDevice));
-  PA_HIP(hipMemcpy(d->fcb, fb, (size_t)nout * sizeof(float), hipMemcpyHostToDevice));
-  // the layer2 entry's conv + downsample weights in conv_s2v.hip's register order: [wave 4][fragment
-  // 20][tile 2][lane 64][8] of channel xperm(32 wn + 16 tn + r16), input channels 32 (k & 1) + 8 q + e
-  // (fragment k < 18: tap k / 2; 18, 19: the downsample)
+  if (const int rc = upload(&d->w16, h16.data(), h16.size())) return rc;
+  if (const int rc = upload(&d->w32, h32.data(), h32.size())) return rc;
+  if (const int rc = upload(&d->bias, hb.data(), hb.size())) return rc;
+  if (const int rc = upload(&d->fcw, fw, (size_t)nout * 512)) return rc;
+  if (const int rc = upload(&d->fcb, fb, (size_t)nout)) return rc;
+  // the stride-2 block entries' weights in VGPR-fragment order (pack_vgpr_frags)
   for (const Block& bk : d->blocks) {
+    if (bk.ds < 0) continue;
     const ConvL& c = d->convs[bk.conv1];
-    if (bk.ds < 0 || c.cin != 64 || c.cout != 128 || d->wv2) continue;
     const ConvL& cd = d->convs[bk.ds];
-    std::vector<_Float16> hv((size_t)4 * 20 * 2 * 64 * 8);
-    for (int wn = 0; wn < 4; ++wn)
-      for (int k = 0; k < 20; ++k)
-        for (int tn = 0; tn < 2; ++tn)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int e = 0; e < 8; ++e) {
-              const int q = lane >> 4, r16 = lane & 15, co = xperm_host(32 * wn + 16 * tn + r16);
-              const int ci = 32 * (k & 1) + 8 * q + e;
-              const _Float16 v = k < 18 ? h16[c.w_off + ((size_t)co * 9 + (k >> 1)) * 64 + ci]
-                                        : h16[cd.w_off + (size_t)co * 64 + ci];
-              hv[((((size_t)wn * 20 + k) * 2 + tn) * 64 + lane) * 8 + e] = v;
-            }
-    PA_HIP(hipMalloc(&d->wv2, hv.size() * sizeof(_Float16)));
-    PA_HIP(hipMemcpy(d->wv2, hv.data(), hv.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    if (c.cin == 64 && c.cout == 128 && !d->wv2) {
+      // conv_s2v.hip: [wave 4][fragment][tile 2], the wave's 32 weight rows in cout_perm order
+      const auto hv = pack_vgpr_frags(&h16[c.w_off], &h16[cd.w_off], 64, 4, [](int wn, int tn, int r16) {
+        return FragRow{cout_perm(32 * wn + 16 * tn + r16), 0};
+      });
+      if (const int rc = upload(&d->wv2, hv.data(), hv.size())) return rc;
+      // conv_x3s2v.hip: [wave 8][fragment][plane 2] of channel 16 wave + r16, [hi (64) | lo (64)] per tap
+      const auto hx = pack_vgpr_frags(&h3[c.w3_off], &h3[cd.w3_off], 128, 8, [](int wn, int pl, int r16) {
+        return FragRow{16 * wn + r16, 64 * pl};
+      });
+      if (const int rc = upload(&d->wv2x3, hx.data(), hx.size())) return rc;
+    }
+    if (c.cin == 128 && c.cout == 256 && !d->wv3x3) {
+      // conv_x3s2k.hip: [quarter h 4][block wb 2][tile wc 4][fragment][plane 2] of channel 64 h + 16 wc + r16,
+      // input block wb of [hi (128) | lo (128)] per tap
+      const auto hx = pack_vgpr_frags(&h3[c.w3_off], &h3[cd.w3_off], 256, 4 * 2 * 4, [](int o, int pl, int r16) {
+        const int h = o >> 3, wb = (o >> 2) & 1, wc = o & 3;
+        return FragRow{64 * h + 16 * wc + r16, 128 * pl + 64 * wb};
+      });
+      if (const int rc = upload(&d->wv3x3, hx.data(), hx.size())) return rc;
+    }
   }
-  // the fp16x3 layer2 entry's hi / lo planes in conv_x3s2v.hip's register order: [wave 8][fragment
-  // 20][plane 2][lane 64][8] of channel 16 wave + r16, input channels 32 (k & 1) + 8 q + e (fragment
-  // k < 18: tap k / 2; 18, 19: the downsample)
-  for (const Block& bk : d->blocks) {
-    const ConvL& c = d->convs[bk.conv1];
-    if (bk.ds < 0 || c.cin != 64 || c.cout != 128 || d->wv2x3) continue;
-    const ConvL& cd = d->convs[bk.ds];
-    std::vector<_Float16> hv((size_t)8 * 20 * 2 * 64 * 8);
-    for (int wn = 0; wn < 8; ++wn)
-      for (int k = 0; k < 20; ++k)
-        for (int pl = 0; pl < 2; ++pl)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int e = 0; e < 8; ++e) {
-              const int q = lane >> 4, r16 = lane & 15, co = 16 * wn + r16, ci = 32 * (k & 1) + 8 * q + e;
-              const _Float16 v = k < 18 ? h3[c.w3_off + ((size_t)co * 9 + (k >> 1)) * 128 + pl * 64 + ci]
-                                        : h3[cd.w3_off + (size_t)co * 128 + pl * 64 + ci];
-              hv[((((size_t)wn * 20 + k) * 2 + pl) * 64 + lane) * 8 + e] = v;
-            }
-    PA_HIP(hipMalloc(&d->wv2x3, hv.size() * sizeof(_Float16)));
-    PA_HIP(hipMemcpy(d->wv2x3, hv.data(), hv.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-  }
-  // the fp16x3 layer3 entry's in conv_x3s2k.hip's order: [quarter h][block wb][tile wc][fragment
-  // 20][plane 2][lane 64][8] of channel 64 h + 16 wc + r16, input channels 64 wb + 32 (k & 1) + 8 q + e
-  for (const Block& bk : d->blocks) {
-    const ConvL& c = d->convs[bk.conv1];
-    if (bk.ds < 0 || c.cin != 128 || c.cout != 256 || d->wv3x3) continue;
-    const ConvL& cd = d->convs[bk.ds];
-    std::vector<_Float16> hv((size_t)4 * 2 * 4 * 20 * 2 * 64 * 8);
-    for (int hh = 0; hh < 4; ++hh)
-      for (int wb = 0; wb < 2; ++wb)
-        for (int wc = 0; wc < 4; ++wc)
-          for (int k = 0; k < 20; ++k)
-            for (int pl = 0; pl < 2; ++pl)
-              for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                  const int q = lane >> 4, r16 = lane & 15, co = 64 * hh + 16 * wc + r16;
-                  const int ci = 64 * wb + 32 * (k & 1) + 8 * q + e;
-                  const _Float16 v = k < 18 ? h3[c.w3_off + ((size_t)co * 9 + (k >> 1)) * 256 + pl * 128 + ci]
-                                            : h3[cd.w3_off + (size_t)co * 256 + pl * 128 + ci];
-                  hv[((((((size_t)hh * 2 + wb) * 4 + wc) * 20 + k) * 2 + pl) * 64 + lane) * 8 + e] = v;
-                }
-    PA_HIP(hipMalloc(&d->wv3x3, hv.size() * sizeof(_Float16)));
-    PA_HIP(hipMemcpy(d->wv3x3, hv.data(), hv.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-  }
-  PA_HIP(hipMalloc(&d->w3, h3.size() * sizeof(_Float16)));
-  PA_HIP(hipMalloc(&d->scl, hs.size() * sizeof(float)));
-  PA_HIP(hipMalloc(&d->bstem3, hbs.size() * sizeof(float)));
-  PA_HIP(hipMemcpy(d->w3, h3.data(), h3.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-  PA_HIP(hipMemcpy(d->scl, hs.data(), hs.size() * sizeof(float), hipMemcpyHostToDevice));
-  PA_HIP(hipMemcpy(d->bstem3, hbs.data(), hbs.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (const int rc = upload(&d->w3, h3.data(), h3.size())) return rc;
+  if (const int rc = upload(&d->scl, hs.data(), hs.size())) return rc;
+  if (const int rc = upload(&d->bstem3, hbs.data(), hbs.size())) return rc;
   if (!d->tctr) {
     PA_HIP(hipMalloc(&d->tctr, 64 * sizeof(unsigned)));
     PA_HIP(hipMemset(d->tctr, 0, 64 * sizeof(unsigned)));

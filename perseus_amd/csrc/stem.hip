@@ -17,12 +17,11 @@
 // 59 and 41 us per batch-64 launch against this one's 35; removed.)
 #include <type_traits>
 
-#include "conv_gx.h"
+#include "conv.h"
 #include "rgb_src.h"
 
 namespace pa {
 
-typedef unsigned su32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 
 namespace stem {
@@ -32,19 +31,6 @@ constexpr int PW = 262;       // ring row width in pixels (wi = c - 3)
 constexpr int ROWB = PW * 8;  // bytes per ring row (4 x fp16 per pixel)
 constexpr int CROWB = 128 * 128;          // one conv row: 128 px x 64 ch fp16
 }  // namespace stem
-
-__device__ __forceinline__ int crow_swz(int px, int chunk) { return px * 128 + ((chunk ^ ((px >> 1) & 7)) << 4); }
-
-template <int V>
-using stc = std::integral_constant<int, V>;
-
-template <int B, int E, typename F>
-__device__ __forceinline__ void stem_for(F&& f) {
-  if constexpr (B < E) {
-    f(stc<B>{});
-    stem_for<B + 1, E>(f);
-  }
-}
 
 // Version 3: weights in VGPRs, vertical pooling in registers.  Wave w owns conv
 // columns [16w, 16w + 16) of BOTH rows of every pair (2p, 2p + 1), so it forms the
@@ -170,11 +156,11 @@ __global__ __launch_bounds__(512) void stem_pool3_fp16(const float* __restrict__
   if (tid < 64) bl[tid] = bv;
   xwait_vm<2 * (D - 1)>();  // this wave's weight DMAs (only the prefetch may stay in flight)
   lds_barrier();
-  su32x4 wf[7][TN];
+  u32x4 wf[7][TN];
 #pragma unroll
   for (int kh = 0; kh < 7; ++kh)
 #pragma unroll
-    for (int tn = 0; tn < TN; ++tn) wf[kh][tn] = *reinterpret_cast<const su32x4*>(wst + (kh * 4 + tn) * 1024 + lane * 16);
+    for (int tn = 0; tn < TN; ++tn) wf[kh][tn] = *reinterpret_cast<const u32x4*>(wst + (kh * 4 + tn) * 1024 + lane * 16);
   if constexpr (DBG == 4) trace_stamp(trace, 1);
 
   const int wo = wid * 16 + r16;  // this lane's conv column
@@ -182,7 +168,7 @@ __global__ __launch_bounds__(512) void stem_pool3_fp16(const float* __restrict__
   const int qc = tid >> 3, c8 = tid & 7;
   half4 prev[TN];  // post-ReLU conv row 2p - 1 (this lane's column, 4 channels per tile)
 
-  stem_for<0, PBT + 2>([&](auto jc) __attribute__((always_inline)) {
+  const_for<0, PBT + 2>([&](auto jc) __attribute__((always_inline)) {
     constexpr int j = decltype(jc)::value;
     const int r0 = 2 * p0 - 2 + 2 * j;  // pair j: conv rows r0 = 2p, r0 + 1 (p = p0 - 1 + j)
     const int hs = 4 * p0 - 7 + 4 * j;
@@ -196,11 +182,11 @@ __global__ __launch_bounds__(512) void stem_pool3_fp16(const float* __restrict__
           for (int b = 0; b < TN; ++b) acc[a][b] = *reinterpret_cast<const f32x4*>(bl + b * 16 + q * 4);
 #pragma unroll
         for (int kh = 0; kh < 7; ++kh) {
-          su32x4 fb[2];
+          u32x4 fb[2];
 #pragma unroll
           for (int t = 0; t < 2; ++t) {
             const int slot = (hs + 2 * t + kh + 64) & (RING - 1);
-            fb[t] = *reinterpret_cast<const su32x4*>(ring + slot * ROWB + (2 * wo) * 8 + q * 16);
+            fb[t] = *reinterpret_cast<const u32x4*>(ring + slot * ROWB + (2 * wo) * 8 + q * 16);
           }
 #pragma unroll
           for (int t = 0; t < 2; ++t)
@@ -218,9 +204,9 @@ __global__ __launch_bounds__(512) void stem_pool3_fp16(const float* __restrict__
       if constexpr (j >= 2 && DBG != 2) {
         const int p = p0 + j - 2;
         const char* vr = vring + ((j - 1) & 1) * CROWB;
-        half8 m = *reinterpret_cast<const half8*>(vr + crow_swz(2 * qc, c8));
-        m = __builtin_elementwise_max(m, *reinterpret_cast<const half8*>(vr + crow_swz(2 * qc + 1, c8)));
-        if (qc > 0) m = __builtin_elementwise_max(m, *reinterpret_cast<const half8*>(vr + crow_swz(2 * qc - 1, c8)));
+        half8 m = *reinterpret_cast<const half8*>(vr + tile_swz(2 * qc, c8));
+        m = __builtin_elementwise_max(m, *reinterpret_cast<const half8*>(vr + tile_swz(2 * qc + 1, c8)));
+        if (qc > 0) m = __builtin_elementwise_max(m, *reinterpret_cast<const half8*>(vr + tile_swz(2 * qc - 1, c8)));
         store16<WT>(out, (unsigned)(((((size_t)n * 64 + p) * 64 + qc) * 64 + c8 * 8) * 2), m);
       }
     };
@@ -256,7 +242,7 @@ __global__ __launch_bounds__(512) void stem_pool3_fp16(const float* __restrict__
         for (int tn = 0; tn < TN; ++tn) {
           const half4 vv = __builtin_elementwise_max(prev[tn], __builtin_elementwise_max(v0[tn], v1[tn]));
           const int c = tn * 16 + q * 4;
-          *reinterpret_cast<half4*>(vw + crow_swz(wo, c >> 3) + (c & 7) * 2) = vv;
+          *reinterpret_cast<half4*>(vw + tile_swz(wo, c >> 3) + (c & 7) * 2) = vv;
         }
       }
 #pragma unroll
@@ -523,16 +509,16 @@ __global__ __launch_bounds__(512) void stem_role_fp16(const float* __restrict__ 
 
   constexpr int TN = 4;
   if (!mover) {
-    su32x4 wf[7][TN];
+    u32x4 wf[7][TN];
 #pragma unroll
     for (int kh = 0; kh < 7; ++kh)
 #pragma unroll
-      for (int tn = 0; tn < TN; ++tn) wf[kh][tn] = *reinterpret_cast<const su32x4*>(wst + (kh * 4 + tn) * 1024 + lane * 16);
+      for (int tn = 0; tn < TN; ++tn) wf[kh][tn] = *reinterpret_cast<const u32x4*>(wst + (kh * 4 + tn) * 1024 + lane * 16);
     half4 prev[2][TN];  // post-ReLU conv row 2p - 1, per column tile
     f32x4 breg[TN];
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) breg[tn] = BR ? *reinterpret_cast<const f32x4*>(bl + tn * 16 + q * 4) : f32x4{};
-    stem_for<0, PBT + 1>([&](auto jc) __attribute__((always_inline)) {
+    const_for<0, PBT + 1>([&](auto jc) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
       const int r0 = 2 * p0 - 2 + 2 * j;  // pair j: conv rows r0 = 2p, r0 + 1 (p = p0 - 1 + j)
       const int hs = 4 * p0 - 7 + 4 * j;
@@ -548,10 +534,10 @@ __global__ __launch_bounds__(512) void stem_role_fp16(const float* __restrict__ 
         }
         // the 9 input rows of this pair (row t + kh for conv row t, tap row kh), each read
         // once and four taps' MFMAs (two tap rows) ahead of its first use
-        su32x4 fr[9];
+        u32x4 fr[9];
         auto rd = [&](int r) __attribute__((always_inline)) {
           const int slot = (hs + r + 64) & (RING - 1);
-          fr[r] = *reinterpret_cast<const su32x4*>(ring + slot * ROWB + (2 * (wid * 32 + c * 16 + r16)) * 8 + q * 16);
+          fr[r] = *reinterpret_cast<const u32x4*>(ring + slot * ROWB + (2 * (wid * 32 + c * 16 + r16)) * 8 + q * 16);
         };
 #pragma unroll
         for (int r = 0; r < 4; ++r) rd(r);
@@ -595,7 +581,7 @@ __global__ __launch_bounds__(512) void stem_role_fp16(const float* __restrict__ 
           const half4 vv = __builtin_elementwise_max(__builtin_elementwise_max(prev[c][tn], v0),
                                                      __builtin_elementwise_max(v1, z4));
           const int ch = tn * 16 + q * 4;
-          *reinterpret_cast<half4*>(vw + crow_swz(wo, ch >> 3) + (ch & 7) * 2) = vv;
+          *reinterpret_cast<half4*>(vw + tile_swz(wo, ch >> 3) + (ch & 7) * 2) = vv;
         }
         prev[c][tn] = v1;
       };
@@ -626,7 +612,7 @@ __global__ __launch_bounds__(512) void stem_role_fp16(const float* __restrict__ 
       if (tid == 0) trace[(blockIdx.y * gridDim.x + blockIdx.x) * 64 + 59] = __builtin_amdgcn_s_memtime();
     }
   } else {
-    stem_for<0, PBT + 2>([&](auto jc) __attribute__((always_inline)) {
+    const_for<0, PBT + 2>([&](auto jc) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
       const int hs = 4 * p0 - 7 + 4 * j;
       if constexpr (DBG == 5) {  // timing only: movers idle (barriers only), wrong results
@@ -641,9 +627,9 @@ __global__ __launch_bounds__(512) void stem_role_fp16(const float* __restrict__ 
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int e = mt + 256 * h, qc = e >> 3, c8 = e & 7;
-          half8 m = *reinterpret_cast<const half8*>(vr + crow_swz(2 * qc, c8));
-          m = __builtin_elementwise_max(m, *reinterpret_cast<const half8*>(vr + crow_swz(2 * qc + 1, c8)));
-          if (qc > 0) m = __builtin_elementwise_max(m, *reinterpret_cast<const half8*>(vr + crow_swz(2 * qc - 1, c8)));
+          half8 m = *reinterpret_cast<const half8*>(vr + tile_swz(2 * qc, c8));
+          m = __builtin_elementwise_max(m, *reinterpret_cast<const half8*>(vr + tile_swz(2 * qc + 1, c8)));
+          if (qc > 0) m = __builtin_elementwise_max(m, *reinterpret_cast<const half8*>(vr + tile_swz(2 * qc - 1, c8)));
           store16<true>(out, (unsigned)(((((size_t)n * 64 + p) * 64 + qc) * 64 + c8 * 8) * 2), m);
         }
       }

@@ -13,7 +13,7 @@
 // planes (2 x 28 KB; 112 VGPRs per plane would not fit next to the f32 epilogue) and
 // one f32 V row (32 KB) -- so the V row is single-buffered, and each pair has two
 // barriers (V row free / V row written) instead of one.
-#include "conv_gx.h"
+#include "conv.h"
 
 namespace pa {
 
@@ -27,9 +27,6 @@ constexpr int ROWB = PW * 8;          // one plane's ring row: 4 x fp16 per pixe
 constexpr int VROWB = 128 * 256;      // f32 V row: 128 px x 64 ch x 4 B
 constexpr int WPLANE = 28 * 1024;     // one weight plane in A-fragment order (7 kh x 4 tn blocks)
 }  // namespace stemx3
-
-// f32 V row: pixel px = 16 chunks of 16 B (4 channels), XOR-swizzled by px
-__device__ __forceinline__ int vswz(int px, int chunk) { return px * 256 + ((chunk ^ (px & 15)) << 4); }
 
 template <int PBT, int D>
 __global__ __launch_bounds__(512) void stem_pool3_x3(const float* __restrict__ x, int B, int Cin,
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(512) void stem_pool3_x3(const float* __restrict__ x
   f32x4 prev[TN];  // post-ReLU conv row 2p - 1 (this lane's column, 4 channels per tile)
   f32x4 vv[TN];
 
-  gx_for<0, PBT + 1>([&](auto jc) __attribute__((always_inline)) {
+  const_for<0, PBT + 1>([&](auto jc) __attribute__((always_inline)) {
     constexpr int j = decltype(jc)::value;
     const int r0 = 2 * p0 - 2 + 2 * j;  // pair j: conv rows r0 = 2p, r0 + 1 (p = p0 - 1 + j)
     const int hs = 4 * p0 - 7 + 4 * j;
@@ -172,20 +169,20 @@ __global__ __launch_bounds__(512) void stem_pool3_x3(const float* __restrict__ x
     lds_barrier();  // every wave is past its conv reads (ring) and the last pool's reads (V row)
     if constexpr (j >= 1) {
 #pragma unroll
-      for (int tn = 0; tn < TN; ++tn) *reinterpret_cast<f32x4*>(vrow + vswz(wo, tn * 4 + q)) = vv[tn];
+      for (int tn = 0; tn < TN; ++tn) *reinterpret_cast<f32x4*>(vrow + tile_swz256(wo, tn * 4 + q)) = vv[tn];
     }
     if constexpr (j < PBT) store_rows(hs + 9, pf[(j + 1) % D]);
     lds_barrier();
     if constexpr (j >= 1) {  // pooled row p = p0 + j - 1: horizontal max over V pixels 2qc - 1 .. 2qc + 1
       const int p = p0 + j - 1;
-      f32x4 m0 = *reinterpret_cast<const f32x4*>(vrow + vswz(2 * qc, 2 * c8));
-      f32x4 m1 = *reinterpret_cast<const f32x4*>(vrow + vswz(2 * qc, 2 * c8 + 1));
+      f32x4 m0 = *reinterpret_cast<const f32x4*>(vrow + tile_swz256(2 * qc, 2 * c8));
+      f32x4 m1 = *reinterpret_cast<const f32x4*>(vrow + tile_swz256(2 * qc, 2 * c8 + 1));
 #pragma unroll
       for (int dx = 0; dx < 2; ++dx) {
         const int px = dx == 0 ? 2 * qc + 1 : 2 * qc - 1;
         if (px < 0) continue;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(vrow + vswz(px, 2 * c8));
-        const f32x4 b = *reinterpret_cast<const f32x4*>(vrow + vswz(px, 2 * c8 + 1));
+        const f32x4 a = *reinterpret_cast<const f32x4*>(vrow + tile_swz256(px, 2 * c8));
+        const f32x4 b = *reinterpret_cast<const f32x4*>(vrow + tile_swz256(px, 2 * c8 + 1));
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           m0[e] = fmaxf(m0[e], a[e]);
@@ -274,14 +271,14 @@ __global__ __launch_bounds__(512) void stem_role_x3(const float* __restrict__ x,
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int e = mt + 256 * h, qc = e >> 3, c8 = e & 7;
-      f32x4 m0 = *reinterpret_cast<const f32x4*>(vrow + vswz(2 * qc, 2 * c8));
-      f32x4 m1 = *reinterpret_cast<const f32x4*>(vrow + vswz(2 * qc, 2 * c8 + 1));
+      f32x4 m0 = *reinterpret_cast<const f32x4*>(vrow + tile_swz256(2 * qc, 2 * c8));
+      f32x4 m1 = *reinterpret_cast<const f32x4*>(vrow + tile_swz256(2 * qc, 2 * c8 + 1));
 #pragma unroll
       for (int dx = 0; dx < 2; ++dx) {
         const int px = dx == 0 ? 2 * qc + 1 : 2 * qc - 1;
         if (px < 0) continue;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(vrow + vswz(px, 2 * c8));
-        const f32x4 b = *reinterpret_cast<const f32x4*>(vrow + vswz(px, 2 * c8 + 1));
+        const f32x4 a = *reinterpret_cast<const f32x4*>(vrow + tile_swz256(px, 2 * c8));
+        const f32x4 b = *reinterpret_cast<const f32x4*>(vrow + tile_swz256(px, 2 * c8 + 1));
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           m0[k] = fmaxf(m0[k], a[k]);
@@ -343,7 +340,7 @@ __global__ __launch_bounds__(512) void stem_role_x3(const float* __restrict__ x,
   constexpr int TN = 4;
   if (!mover) {
     f32x4 prev[2][TN];  // post-ReLU conv row 2p - 1, per column tile
-    gx_for<0, PBT + 1>([&](auto jc) __attribute__((always_inline)) {
+    const_for<0, PBT + 1>([&](auto jc) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
       const int r0 = 2 * p0 - 2 + 2 * j;  // pair j: conv rows r0 = 2p, r0 + 1 (p = p0 - 1 + j)
       const int hs = 4 * p0 - 7 + 4 * j;
@@ -410,12 +407,12 @@ __global__ __launch_bounds__(512) void stem_role_x3(const float* __restrict__ x,
         for (int c = 0; c < 2; ++c)
 #pragma unroll
           for (int tn = 0; tn < TN; ++tn)
-            *reinterpret_cast<f32x4*>(vrow + vswz(wid * 32 + c * 16 + r16, tn * 4 + q)) = vv[c][tn];
+            *reinterpret_cast<f32x4*>(vrow + tile_swz256(wid * 32 + c * 16 + r16, tn * 4 + q)) = vv[c][tn];
       }
       lds_barrier();  // B: V(j) written
     });
   } else {
-    gx_for<0, PBT + 1>([&](auto jc) __attribute__((always_inline)) {
+    const_for<0, PBT + 1>([&](auto jc) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
       const int hs = 4 * p0 - 7 + 4 * j;
       if constexpr (j + D <= PBT) load_rows(hs + 9 + 4 * (D - 1), pf[j % D]);  // pair j + D's new rows
