@@ -224,6 +224,13 @@ int pa_dyn_linearize(int n, const double* t1_dev, const double* w_dev, const dou
                      double* r_dev, double* j0_dev, double* j1_dev, double* j2_dev, double* j3_dev,
                      double* err_dev, void* stream);
 
+/* pa_dyn_linearize with one dt per factor: dt_dev (n) device doubles (not validated: a
+ * non-finite dt gives that factor NaN outputs). */
+int pa_dyn_linearize_dt(int n, const double* t1_dev, const double* w_dev, const double* v_dev,
+                        const double* t2_dev, const double* dt_dev, int vel_frame, const double* inv_sigma_dev,
+                        double* r_dev, double* j0_dev, double* j1_dev, double* j2_dev, double* j3_dev,
+                        double* err_dev, void* stream);
+
 /* ConstantVelocityFactor (factors.py:160-171): r = v2 - v1, J0 = -I3, J1 = I3. */
 int pa_cv_linearize(int n, const double* v1_dev, const double* v2_dev, const double* inv_sigma_dev,
                     double* r_dev, double* j0_dev, double* j1_dev, double* err_dev, void* stream);
@@ -246,7 +253,37 @@ int pa_cv_linearize(int n, const double* v1_dev, const double* v2_dev, const dou
  * zero-initialised pair means none, so callers that never set them keep the plain factors.
  * Every entry point that takes a pa_traj_args (pa_trajectory_linearize, pa_trajectory_lm_solve,
  * pa_window_lm_solve, pa_window_pose_tick and its _pre / _post / _reduce forms) honours them
- * and rejects a bad pair with PA_EINVAL. */
+ * and rejects a bad pair with PA_EINVAL.
+ * dt_pair / kp_mask: real timestamps (cameras drop frames, so consecutive frames are 1, 2 or 3
+ * periods apart, and a hand hides single corners).  Both are device arrays read at every launch,
+ * optional and independent; zero-initialised means none, as for the robust pair.
+ *   dt_pair: the PoseDynamicsFactor of pair (l, l+1) of trajectory t uses dt_pair[t*(L-1)+l]
+ *     instead of dt.  The contents are not validated on the host: a non-finite or non-positive
+ *     value gives NaN factors and a non-zero info downstream, as a NaN pose does.
+ *   kp_mask: bit k of kp_mask[t*L+l] set = keypoint k of frame l was measured.  A cleared bit gives
+ *     that projection factor status 2 and r = J = err = 0, exactly the bits nvalid gives a frame
+ *     outside the filled part; the two combine by OR of "off", and off wins over cheirality (a
+ *     masked factor behind the camera has status 2, not 1).  Requires n_kp <= 32 (PA_EINVAL
+ *     otherwise); bits at and above n_kp are ignored.
+ *   dt_new / mask_new (T each): what the entry points that ADVANCE the window (pa_window_pose_tick,
+ *     pa_window_pose_tick_pre and their _prior forms) store as the new last pair's dt and the
+ *     new last frame's mask after shifting both rings one frame towards l = 0 with the window;
+ *     dt_new[t] also predicts the new frame.  They return PA_EINVAL before any launch when
+ *     exactly one of (dt_pair, dt_new) or exactly one of (kp_mask, mask_new) is NULL.  Every
+ *     other entry point ignores the _new pair: pa_trajectory_linearize, the four LM solves and
+ *     pa_window_pose_tick_reduce(_prior) do not advance, and pa_window_pose_tick_post lands the
+ *     new keypoints on the frame its pre half already advanced, reading kp_mask there (it must be
+ *     given the same dt_pair / kp_mask pointers as the pre half).  On the newest frame of a pre
+ *     half the order of statuses is unchanged: the mask gives 2, the pre half then stamps 3 on
+ *     all of that frame, and the post half re-evaluates with the mask.
+ * A frame without any measured keypoint is held by its two dynamics factors and the constant-
+ * velocity factors alone.  Its rotation is then NOT observable from this factor set: nothing
+ * couples successive angular velocities (ConstantVelocityFactor is on the linear velocity only),
+ * so frame l's rotation and the angular velocities of frames l-1 and l can move together at no
+ * cost: 9 equations for the frame's 12 unknowns.  Such a frame needs a lambda of the streaming
+ * tick's order (1e-2), exactly as a partly filled window does (see pa_trajectory_marginals); the
+ * tick then holds it at its prediction.  pa_trajectory_gn_step, pa_trajectory_marginals and
+ * pa_window_marginalize consume statuses and factor outputs only and need nothing else. */
 typedef struct pa_traj_args {
   int T, L, n_kp, H, W;
   const float* y;          /* (T*L, 2K) normalized keypoints */
@@ -265,6 +302,13 @@ typedef struct pa_traj_args {
   int32_t* status;
   double *r_dyn, *j_dyn0, *j_dyn1, *j_dyn2, *j_dyn3, *err_dyn;
   double *r_cv, *j_cv0, *j_cv1, *err_cv;
+  /* real timestamps (all four NULL = none: every kernel, output bit and captured graph is then what
+   * it was before these fields existed).  They stand before nvalid, not at the struct's end: the
+   * struct still ends in nvalid, robust_proj, robust_proj_k, which tests/test_robust_capi.py pins. */
+  const double* dt_pair;     /* (T*(L-1)) or NULL: pair (l, l+1) of trajectory t uses dt_pair[t*(L-1)+l], not dt */
+  const uint32_t* kp_mask;   /* (T*L) or NULL: bit k of word t*L+l set = keypoint k of that frame was measured */
+  const double* dt_new;      /* (T): the new last pair's dt; read only by entry points that advance the window */
+  const uint32_t* mask_new;  /* (T): the new last frame's mask; read only by entry points that advance */
   const int32_t* nvalid;   /* (T) or NULL: frames with measurements, from the window's end */
   int robust_proj;         /* PA_ROBUST_*: the projection factors' robust noise model (0 = none) */
   double robust_proj_k;    /* its k > 0, in whitened units (host scalar; ignored for PA_ROBUST_NONE) */
@@ -398,6 +442,16 @@ int pa_window_advance(int T, int L, int n_kp, const float* y_new_dev, float* y_d
 int pa_window_advance_n(int T, int L, int n_kp, const float* y_new_dev, float* y_dev, double* pose_dev,
                         double* angvel_dev, double* vel_dev, int32_t* nvalid_dev, double dt, int vel_frame,
                         void* stream);
+/* pa_window_advance_n with the rings of pa_traj_args' real timestamps: dt_pair_dev (T*(L-1)) and
+ * kp_mask_dev (T*L) shift one frame towards l = 0 with the window, dt_new_dev[t] lands at pair
+ * L-2 and mask_new_dev[t] at frame L-1, and frame L-1 is predicted with dt_new_dev[t] instead
+ * of dt.  Either ring may be absent: (dt_pair_dev, dt_new_dev) are given together or both NULL,
+ * and so are (kp_mask_dev, mask_new_dev), else PA_EINVAL before any launch; without the dt ring
+ * the prediction uses dt.  nvalid_dev may be NULL. */
+int pa_window_advance_t(int T, int L, int n_kp, const float* y_new_dev, float* y_dev, double* pose_dev,
+                        double* angvel_dev, double* vel_dev, int32_t* nvalid_dev, double* dt_pair_dev,
+                        uint32_t* kp_mask_dev, const double* dt_new_dev, const uint32_t* mask_new_dev, double dt,
+                        int vel_frame, void* stream);
 int pa_window_retract(int T, int L, const double* delta_dev, const int32_t* info_dev, double* pose_dev,
                       double* angvel_dev, double* vel_dev, void* stream);
 /* pa_window_retract that also writes each trajectory's newest (last-frame) pose after the

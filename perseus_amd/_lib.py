@@ -31,8 +31,9 @@ class TrajArgs(C.Structure):
                 ("isig_cv", C.c_void_p), ("r_proj", C.c_void_p), ("j_proj", C.c_void_p), ("err_proj", C.c_void_p),
                 ("status", C.c_void_p), ("r_dyn", C.c_void_p), ("j_dyn0", C.c_void_p), ("j_dyn1", C.c_void_p),
                 ("j_dyn2", C.c_void_p), ("j_dyn3", C.c_void_p), ("err_dyn", C.c_void_p), ("r_cv", C.c_void_p),
-                ("j_cv0", C.c_void_p), ("j_cv1", C.c_void_p), ("err_cv", C.c_void_p), ("nvalid", C.c_void_p),
-                ("robust_proj", C.c_int), ("robust_proj_k", C.c_double)]
+                ("j_cv0", C.c_void_p), ("j_cv1", C.c_void_p), ("err_cv", C.c_void_p),
+                ("dt_pair", C.c_void_p), ("kp_mask", C.c_void_p), ("dt_new", C.c_void_p), ("mask_new", C.c_void_p),
+                ("nvalid", C.c_void_p), ("robust_proj", C.c_int), ("robust_proj_k", C.c_double)]
 
 
 class LMParams(C.Structure):
@@ -141,6 +142,8 @@ _SIGS = {
                                                                                      C.c_void_p]),
     "pa_window_advance_n": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double, C.c_int,
                                                                                        C.c_void_p]),
+    "pa_window_advance_t": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_double, C.c_int,
+                                                                                        C.c_void_p]),
     "pa_window_retract": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 6),
     "pa_debug_gn_set_assemblers": (C.c_int, [C.c_int]),
     "pa_window_retract_newest": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 7),
@@ -163,6 +166,9 @@ _SIGS = {
     "pa_dyn_linearize": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pa_dyn_linearize_dt": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "pa_cv_linearize": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/perseus_amd_loader.h (host pointers)

@@ -76,7 +76,7 @@ __device__ __forceinline__ FactorSet factor_set_select(const FactorSet& a, const
 
 // trajectory t's factors: the arrays of a T = 1 problem start at its records.  The state
 // (y, pose, vel, angvel) is ta's, the factor outputs are s's (factor_set(ta): ta's own); a
-// null nvalid stays null, and so does a null output (err_*, the projection arrays at K = 0)
+// null nvalid / dt_pair / kp_mask / dt_new / mask_new stays null, and so does a null output (err_*, the projection arrays at K = 0)
 // unless the caller knows that s has none (NULLS = false: no tests; lm_lin_kernel, which is
 // at the edge of its register budget).
 template <bool NULLS = true>
@@ -94,6 +94,11 @@ __device__ __forceinline__ pa_traj_args traj_view(const pa_traj_args& ta, int t,
   PA_FACTOR_OUTPUTS(PA_X)
 #undef PA_X
   a1.nvalid = off(ta.nvalid, (long)t);
+  // the real timestamps (read only by the TM instantiations, factors_dev.h)
+  a1.dt_pair = off(ta.dt_pair, d0);
+  a1.kp_mask = off(ta.kp_mask, f0);
+  a1.dt_new = off(ta.dt_new, (long)t);
+  a1.mask_new = off(ta.mask_new, (long)t);
   return a1;
 }
 

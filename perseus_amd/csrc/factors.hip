@@ -70,18 +70,19 @@ __global__ __launch_bounds__(64) void proj_kernel(int n, const double* __restric
 // mode (pa_debug_trajectory_linearize, timing only): 1 = dynamics workgroups only,
 // 2 = projection / constant-velocity workgroups only
 // RB: the projection factors carry a robust noise model (a.robust_proj; chosen on the host)
-template <bool RB>
+// TM: the launch carries real timestamps (a.dt_pair / a.kp_mask; chosen on the host, factors_dev.h)
+template <bool RB, bool TM>
 __global__ __launch_bounds__(128, 2) void traj_all_kernel(pa_traj_args a, int mode, unsigned long long* ts) {
   __shared__ __attribute__((aligned(16))) double st[trj::STAGE];
   const long wd = ((long)a.T * (a.L - 1) + 63) / 64;
   if ((long)blockIdx.x < wd) {
     if (mode == 2) return;
-    traj_dyn_block(a, blockIdx.x, st, ts);
+    traj_dyn_block<TM>(a, blockIdx.x, st, ts);
   } else if (mode == 1) {
     return;
   } else {
     const int wv = threadIdx.x >> 6;
-    traj_unit_wave<RB>(a, 2 * ((long)blockIdx.x - wd) + wv, st + wv * trj::UNIT, ts);
+    traj_unit_wave<RB, TM>(a, 2 * ((long)blockIdx.x - wd) + wv, st + wv * trj::UNIT, ts);
   }
 }
 
@@ -95,6 +96,14 @@ __global__ __launch_bounds__(256) void window_advance_kernel(int L, int n_kp, co
                                                              float* y, double* pose, double* angvel, double* vel,
                                                              double dt, int vel_frame, int32_t* nvalid) {
   window_advance_body(blockIdx.x, threadIdx.x, 256, L, n_kp, y_new, y, pose, angvel, vel, dt, vel_frame, nvalid);
+}
+
+// with the rings of the real timestamps (pa_window_advance_t)
+__global__ __launch_bounds__(256) void window_advance_t_kernel(int L, int n_kp, const float* __restrict__ y_new,
+                                                               float* y, double* pose, double* angvel, double* vel,
+                                                               double dt, int vel_frame, int32_t* nvalid, AdvRings rg) {
+  window_advance_body<true>(blockIdx.x, threadIdx.x, 256, L, n_kp, y_new, y, pose, angvel, vel, dt, vel_frame, nvalid,
+                            rg);
 }
 
 __global__ __launch_bounds__(64) void window_retract_kernel(int T, int L, const double* __restrict__ delta,
@@ -116,6 +125,21 @@ int pa_window_advance_n(int T, int L, int n_kp, const float* y_new, float* y, do
   PA_CHECK(vel_frame == PA_VEL_WORLD || vel_frame == PA_VEL_BODY, "vel_frame must be 'world' or 'body'.");
   hipLaunchKernelGGL(pa::window_advance_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, L, n_kp, y_new, y, pose,
                      angvel, vel, dt, vel_frame, nvalid);
+  PA_LAUNCH_CHECK();
+  return PA_OK;
+}
+
+int pa_window_advance_t(int T, int L, int n_kp, const float* y_new, float* y, double* pose, double* angvel,
+                        double* vel, int32_t* nvalid, double* dt_pair, uint32_t* kp_mask, const double* dt_new,
+                        const uint32_t* mask_new, double dt, int vel_frame, void* stream) {
+  PA_CHECK(T >= 0 && L >= 1 && n_kp >= 1 && n_kp <= 32, "T=%d L=%d n_kp=%d", T, L, n_kp);
+  PA_CHECK(!dt_pair == !dt_new, "window advance: dt_pair and dt_new are given together (or both NULL)");
+  PA_CHECK(!kp_mask == !mask_new, "window advance: kp_mask and mask_new are given together (or both NULL)");
+  if (T == 0) return PA_OK;
+  PA_CHECK(y_new && y && pose && angvel && vel, "null pointer");
+  PA_CHECK(vel_frame == PA_VEL_WORLD || vel_frame == PA_VEL_BODY, "vel_frame must be 'world' or 'body'.");
+  hipLaunchKernelGGL(pa::window_advance_t_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, L, n_kp, y_new, y, pose,
+                     angvel, vel, dt, vel_frame, nvalid, pa::AdvRings{dt_pair, kp_mask, dt_new, mask_new});
   PA_LAUNCH_CHECK();
   return PA_OK;
 }
@@ -176,7 +200,11 @@ int pa_debug_trajectory_linearize(const pa_traj_args* a, int mode, unsigned long
   PA_CHECK(a->vel_frame == PA_VEL_WORLD || a->vel_frame == PA_VEL_BODY, "vel_frame must be 'world' or 'body'.");
   const long np = (long)a->T * a->L * a->n_kp, nd = (long)a->T * (a->L - 1);
   const long units = (np + 64 * pa::trj::PPW - 1) / (64 * pa::trj::PPW) + (nd + 63) / 64;  // projection | const-vel, two per workgroup
-  const auto kernel = a->robust_proj == PA_ROBUST_NONE ? pa::traj_all_kernel<false> : pa::traj_all_kernel<true>;
+  PA_CHECK(!a->kp_mask || a->n_kp <= 32, "trajectory linearize: kp_mask holds one bit per keypoint, n_kp %d > 32",
+           a->n_kp);
+  const bool rb = a->robust_proj != PA_ROBUST_NONE, tm = a->dt_pair || a->kp_mask;
+  const auto kernel = tm ? (rb ? pa::traj_all_kernel<true, true> : pa::traj_all_kernel<false, true>)
+                         : (rb ? pa::traj_all_kernel<true, false> : pa::traj_all_kernel<false, false>);
   hipLaunchKernelGGL(kernel, dim3((unsigned)((nd + 63) / 64 + (units + 1) / 2)), dim3(128), 0, (hipStream_t)stream, *a,
                      mode, trace);
   PA_LAUNCH_CHECK();

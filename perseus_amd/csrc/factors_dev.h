@@ -614,6 +614,24 @@ __device__ __forceinline__ void traj_stamp(unsigned long long* ts, int slot) {
 // queue before the next round could be issued)
 __device__ __forceinline__ void wave_sync() { asm volatile("" ::: "memory"); }
 
+// TM, on every function and kernel below that takes it: the launch carries real timestamps
+// (a.dt_pair and / or a.kp_mask, include/perseus_amd.h); the host picks the instantiation.  TM =
+// false is token for token the code it was before they existed and never looks at the four
+// fields, so a launch without them runs what it always ran, at the same registers.
+__device__ __forceinline__ bool kp_masked(const uint32_t* kp_mask, long f, int k) {
+  if (!kp_mask) return false;
+  // the frame's word in a vector register: for a uniform frame (pose_tick_post_kernel) it is a
+  // scalar that stays live through the factor, in kernels that are at the scalar-register limit
+  // already (a scalar spill: 36 B of private segment there)
+  uint32_t m = kp_mask[f];
+  asm volatile("" : "+v"(m));
+  return ((m >> k) & 1u) == 0u;
+}
+// (TM only) the whitening pair of a Cam in vector registers, as load_cam does with a robust
+// model's k and for the same reason: the mask's and the rings' pointers are four more scalar pairs
+// in kernels at the scalar-register limit (lm_lin_kernel spilled 68 B, pose_tick_post_kernel 36 B)
+__device__ __forceinline__ void cam_to_vector(Cam& c) { asm volatile("" : "+v"(c.s0), "+v"(c.s1)); }
+
 // 6 x 3 column-major block of a Jacobian: rows 0..2 from `top` (zero if !has_top), rows
 // 3..5 from `bot`, row-scaled by sw (references, not pointers: an address-taken M3 lives
 // in scratch)
@@ -635,6 +653,9 @@ __device__ __forceinline__ void stage6x3(double* J, bool has_top, const M3& top,
 //           dtw = dt A D and H0 = A Ad(inc^-1); writes J1, J2, J0
 // A goes 0 -> 1 through LDS (one barrier).  The products and their order are dyn_one's
 // (factors.py:54-142), so the values are the same; wave 0 holds only the chain and dlog.
+// TM: the factor's own dt (a.dt_pair[jd], per lane: both waves map lane to factor alike, so both
+// see the same value)
+template <bool TM = false>
 __device__ __forceinline__ void traj_dyn_block(const pa_traj_args& a, long blk, double* st, unsigned long long* ts) {
   using namespace trj;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -645,7 +666,11 @@ __device__ __forceinline__ void traj_dyn_block(const pa_traj_args& a, long blk, 
   const long t = jd / (a.L - 1), f = t * a.L + (jd - t * (a.L - 1));
   const bool J = a.j_dyn0 || a.j_dyn1 || a.j_dyn2 || a.j_dyn3;
   const bool world = a.vel_frame == PA_VEL_WORLD;
-  const double dt = a.dt;
+  double dtv = a.dt;
+  if constexpr (TM) {
+    if (a.dt_pair) dtv = a.dt_pair[jd];
+  }
+  const double dt = dtv;
   double sw[6];
 #pragma unroll
   for (int i = 0; i < 6; ++i) sw[i] = a.isig_dyn ? a.isig_dyn[i] : 1.0;
@@ -773,8 +798,9 @@ __device__ __forceinline__ void traj_dyn_block(const pa_traj_args& a, long blk, 
 namespace trj {
 constexpr int PPW = 4;  // projection factors per lane
 }
-// (RB: a.robust_proj names a robust model, proj_eval<true>)
-template <bool RB>
+// (RB: a.robust_proj names a robust model, proj_eval<true>; TM: a.kp_mask switches single
+// projection factors off as a.nvalid does whole frames)
+template <bool RB, bool TM = false>
 __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, double* st, unsigned long long* ts) {
   using trj::PPW;
   const int lane = threadIdx.x & 63;
@@ -788,7 +814,9 @@ __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, do
     int n[PPW];
     // every operand of the PPW factors is loaded before any is used (proj_eval is
     // branch-free, so the loads of all PPW chains are in flight together)
-    const Cam cam = load_cam<RB>(a.K, a.tcam, a.isig_proj, a.robust_proj, a.robust_proj_k);
+    Cam camv = load_cam<RB>(a.K, a.tcam, a.isig_proj, a.robust_proj, a.robust_proj_k);
+    if constexpr (TM) cam_to_vector(camv);
+    const Cam cam = camv;
     Pose T[PPW];
     V3 pb[PPW];
     float2 yv[PPW];
@@ -806,6 +834,7 @@ __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, do
       pb[h] = load3(a.corners + 3 * k);
       const long t = f / a.L;
       off[h] = a.nvalid ? (int)(f - t * a.L) < a.L - a.nvalid[t] : false;
+      if constexpr (TM) off[h] = off[h] || kp_masked(a.kp_mask, f, k);
     }
 #pragma unroll
     for (int h = 0; h < PPW; ++h) {
@@ -878,14 +907,14 @@ __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, do
 constexpr int TICK_LIN_W = 6;
 constexpr int LIN_STAGE = trj::STAGE + 4 * trj::UNIT;
 static_assert(LIN_STAGE * 8 <= 96 * 1024, "factor staging");
-template <bool RB>
+template <bool RB, bool TM = false>
 __device__ __forceinline__ void traj_lin_block(const pa_traj_args& a1, double* st) {
   const int wv = threadIdx.x >> 6;
   const int wp = (a1.L * a1.n_kp + 64 * trj::PPW - 1) / (64 * trj::PPW);  // projection units (<= 2); unit wp: constant velocity
   if (wv < 2) {
-    traj_dyn_block(a1, 0, st, nullptr);  // (its one LDS barrier is matched by every other wave's below)
+    traj_dyn_block<TM>(a1, 0, st, nullptr);  // (its one LDS barrier is matched by every other wave's below)
   } else {
-    if (wv - 2 <= wp) traj_unit_wave<RB>(a1, wv - 2, st + trj::STAGE + (wv - 2) * trj::UNIT, nullptr);
+    if (wv - 2 <= wp) traj_unit_wave<RB, TM>(a1, wv - 2, st + trj::STAGE + (wv - 2) * trj::UNIT, nullptr);
     lds_barrier();
   }
 }
@@ -907,11 +936,34 @@ __device__ __forceinline__ void traj_lin_block(const pa_traj_args& a1, double* s
 // nvalid (optional): frames of the window that hold a real measurement, + 1 per advance up
 // to L (pa_trajectory_linearize skips the projection factors of the others)
 // (the body: trajectory t, thread e of nthr, every thread of the workgroup calls it)
+// TM: the rings of the real timestamps move with the window.  dt_pair (T, L-1) and kp_mask (T, L),
+// each optional: thread l < nthr loads element l + 1 here, before the first barrier, and stores
+// it at l after the rounds (windows longer than the workgroup: further load -> barrier -> store
+// rounds of their own, in increasing order, so again no round stores what a later one reads);
+// thread 0 then lands dt_new[t] / mask_new[t] and predicts with dt_new[t].
 constexpr int ADV_E = 4;
+struct AdvRings {
+  double* dt_pair;
+  uint32_t* kp_mask;
+  const double* dt_new;
+  const uint32_t* mask_new;
+};
+template <bool TM = false>
 __device__ __forceinline__ void window_advance_body(int t, int e, int nthr, int L, int n_kp,
                                                     const float* __restrict__ y_new, float* y, double* pose,
                                                     double* angvel, double* vel, double dt, int vel_frame,
-                                                    int32_t* nvalid) {
+                                                    int32_t* nvalid, const AdvRings rg = AdvRings{}) {
+  [[maybe_unused]] double* dtr = nullptr;
+  [[maybe_unused]] uint32_t* mkr = nullptr;
+  [[maybe_unused]] double ring_dt = 0.0;
+  [[maybe_unused]] uint32_t ring_mk = 0u;
+  if constexpr (TM) {
+    dtr = rg.dt_pair ? rg.dt_pair + (size_t)t * (L - 1) : nullptr;
+    mkr = rg.kp_mask ? rg.kp_mask + (size_t)t * L : nullptr;
+    if (dtr && e < L - 2) ring_dt = dtr[e + 1];
+    if (mkr && e < L - 1) ring_mk = mkr[e + 1];
+    if (dtr && e == 0) dt = rg.dt_new[t];
+  }
   if (nvalid && e == 0) nvalid[t] = nvalid[t] < L ? nvalid[t] + 1 : L;
   // the angular velocity of frame L-2 BEFORE the shift: the newest one a dynamics factor
   // constrains (frame L-1's enters no factor, so its value holds no information); read
@@ -960,6 +1012,23 @@ __device__ __forceinline__ void window_advance_body(int t, int e, int nthr, int 
       }
     }
     __syncthreads();
+  }
+  if constexpr (TM) {
+    if (dtr && e < L - 2) dtr[e] = ring_dt;
+    if (mkr && e < L - 1) mkr[e] = ring_mk;
+    for (int b = nthr; b < L - 1; b += nthr) {  // (uniform; windows longer than the workgroup)
+      const int l = b + e;
+      if (dtr && l < L - 2) ring_dt = dtr[l + 1];
+      if (mkr && l < L - 1) ring_mk = mkr[l + 1];
+      __syncthreads();
+      if (dtr && l < L - 2) dtr[l] = ring_dt;
+      if (mkr && l < L - 1) mkr[l] = ring_mk;
+      __syncthreads();
+    }
+    if (e == 0) {
+      if (dtr && L >= 2) dtr[L - 2] = dt;  // (thread 0's dt is dt_new[t] already)
+      if (mkr) mkr[L - 1] = rg.mask_new[t];
+    }
   }
   if (y_new && e < ny) yt[(L - 1) * ny + e] = y_new[(size_t)t * ny + e];  // (null: the split tick's post half lands it)
   __syncthreads();

@@ -77,8 +77,9 @@ __device__ __forceinline__ void lm_copy(V* dst, const V* src, long n) {
 // launch k = 0: the initial state (ta.pose / vel / angvel) into set 0; k >= 1: the trial state of
 // iteration k into the set that is not current, then the decision.  RB: ta.robust_proj names a
 // robust noise model (the cost is then the sum of its rho; the decision logic is the same).
-// PR: d.pr holds a prior on frame 0
-template <bool RB, bool PR>
+// PR: d.pr holds a prior on frame 0.  TM: ta carries real timestamps (dt_pair / kp_mask,
+// factors_dev.h; traj_view hands the trajectory's slices on)
+template <bool RB, bool PR, bool TM>
 __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta, LmDev d, int k) {
   __shared__ __attribute__((aligned(16))) double st[LIN_STAGE];
   __shared__ int dec_s;
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta
     a1.pose = k > 0 ? d.pose + f0 * 12 : xp;  // (the trial state)
     a1.vel = k > 0 ? d.vel + f0 * 3 : xv;
     a1.angvel = k > 0 ? d.angvel + f0 * 3 : xw;
-    traj_lin_block<RB>(a1, st);
+    traj_lin_block<RB, TM>(a1, st);
     if constexpr (PR) {
       // the prior at frame 0 of the state just linearized: grad to the target set, e_prior to wave 0
       __shared__ double pxi[gn::NV], pes[gn::NV], pe_s;
@@ -363,8 +364,12 @@ static int lm_solve_impl(const pa_traj_args* ta, const pa_lm_params* p, int pend
                           prior->grad, f64(o.pgrad), f64(o.perr), prior->err};
   const hipStream_t s = (hipStream_t)stream;
   const bool rb = ta->robust_proj != PA_ROBUST_NONE;
-  const auto lin_kernel = prior ? (rb ? pa::lm_lin_kernel<true, true> : pa::lm_lin_kernel<false, true>)
-                                : (rb ? pa::lm_lin_kernel<true, false> : pa::lm_lin_kernel<false, false>);
+  const bool tm = ta->dt_pair || ta->kp_mask;
+  const auto lin_kernel =
+      tm ? (prior ? (rb ? pa::lm_lin_kernel<true, true, true> : pa::lm_lin_kernel<false, true, true>)
+                  : (rb ? pa::lm_lin_kernel<true, false, true> : pa::lm_lin_kernel<false, false, true>))
+         : (prior ? (rb ? pa::lm_lin_kernel<true, true, false> : pa::lm_lin_kernel<false, true, false>)
+                  : (rb ? pa::lm_lin_kernel<true, false, false> : pa::lm_lin_kernel<false, false, false>));
   for (int k = 0; k <= p->max_iters; ++k) {
     if (k > 0)
       pa::gn_for_kp(K, [&](auto rp) {

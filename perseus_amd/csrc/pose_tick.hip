@@ -24,16 +24,26 @@ namespace pa {
 // evaluates them on y_new.
 // RB (here and in pose_tick_post_kernel): ta.robust_proj names a robust noise model for the
 // projection factors (proj_eval<true>); the host picks the instantiation.
-template <bool RB>
+// TM (here and in pose_tick_post_kernel): ta carries real timestamps (dt_pair / kp_mask; the host
+// picks the instantiation, factors_dev.h): the advance moves both rings and lands dt_new /
+// mask_new, the factors read them after the barrier that follows it.
+template <bool RB, bool TM>
 __global__ __launch_bounds__(64 * TICK_LIN_W) void pose_tick_lin_kernel(pa_traj_args ta, const float* __restrict__ y_new) {
   __shared__ __attribute__((aligned(16))) double st[LIN_STAGE];
   const int t = blockIdx.x, L = ta.L, K = ta.n_kp;
-  window_advance_body(t, threadIdx.x, 64 * TICK_LIN_W, L, K, y_new, const_cast<float*>(ta.y),
-                      const_cast<double*>(ta.pose), const_cast<double*>(ta.angvel), const_cast<double*>(ta.vel), ta.dt,
-                      ta.vel_frame, const_cast<int32_t*>(ta.nvalid));
+  if constexpr (TM)
+    window_advance_body<true>(t, threadIdx.x, 64 * TICK_LIN_W, L, K, y_new, const_cast<float*>(ta.y),
+                              const_cast<double*>(ta.pose), const_cast<double*>(ta.angvel),
+                              const_cast<double*>(ta.vel), ta.dt, ta.vel_frame, const_cast<int32_t*>(ta.nvalid),
+                              AdvRings{const_cast<double*>(ta.dt_pair), const_cast<uint32_t*>(ta.kp_mask), ta.dt_new,
+                                       ta.mask_new});
+  else
+    window_advance_body(t, threadIdx.x, 64 * TICK_LIN_W, L, K, y_new, const_cast<float*>(ta.y),
+                        const_cast<double*>(ta.pose), const_cast<double*>(ta.angvel), const_cast<double*>(ta.vel), ta.dt,
+                        ta.vel_frame, const_cast<int32_t*>(ta.nvalid));
   __syncthreads();
   const pa_traj_args a1 = traj_view(ta, t, factor_set(ta));
-  traj_lin_block<RB>(a1, st);
+  traj_lin_block<RB, TM>(a1, st);
   if (!y_new) {  // (uniform)
     __syncthreads();  // the unit waves' status stores come first
     if ((int)threadIdx.x < K) a1.status[(long)(L - 1) * K + threadIdx.x] = 3;
@@ -75,7 +85,7 @@ __global__ __launch_bounds__(64 * GN_CR_W, 1) void pose_tick_pre_kernel(GnArgs g
   gn_cr_run<RP, NS, true>(g, blockIdx.x, fb, pool);
 }
 
-template <bool RB>
+template <bool RB, bool TM>
 __global__ __launch_bounds__(64 * GN_CR_W, 1) void pose_tick_post_kernel(pa_traj_args ta, const float* __restrict__ y_new,
                                                                           const double* __restrict__ ws, double* delta,
                                                                           int32_t* info, double* newest) {
@@ -112,12 +122,15 @@ __global__ __launch_bounds__(64 * GN_CR_W, 1) void pose_tick_post_kernel(pa_traj
     // lane k, traj_unit_wave's evaluation
     if (i < ny) const_cast<float*>(ta.y)[fn * ny + i] = y_new[(size_t)t * ny + i];
     if (i < K) {
-      const Cam cam = load_cam<RB>(ta.K, ta.tcam, ta.isig_proj, ta.robust_proj, ta.robust_proj_k);
+      Cam camv = load_cam<RB>(ta.K, ta.tcam, ta.isig_proj, ta.robust_proj, ta.robust_proj_k);
+      if constexpr (TM) cam_to_vector(camv);
+      const Cam cam = camv;
       const Pose T = load_pose(ta.pose + fn * 12);
       const V3 pb = load3(ta.corners + 3 * i);
       const float px = kornia_denorm(y_new[(size_t)t * ny + 2 * i], ta.W);
       const float py = kornia_denorm(y_new[(size_t)t * ny + 2 * i + 1], ta.H);
-      const bool off = ta.nvalid ? L - 1 < L - ta.nvalid[t] : false;
+      bool off = ta.nvalid ? L - 1 < L - ta.nvalid[t] : false;
+      if constexpr (TM) off = off || kp_masked(ta.kp_mask, fn, i);  // (the frame the pre half advanced)
       double r[2], J[12], e;
       int32_t st;
       proj_eval<RB>(T, pb, (double)px, (double)py, cam, r, J, e, st);
@@ -208,15 +221,25 @@ size_t pa_window_pose_tick_workspace(int T, int L) {
 
 // the checks of pa_window_pose_tick, in its order; PA_OK at T == 0 (nothing to do: the caller
 // returns) before the pointers are looked at
-static int pose_tick_check(const pa_traj_args* ta, double lambda, const char* who) {
+// advancing: the entry point moves the window, so the real timestamps' rings need their new
+// elements (dt_pair with dt_new, kp_mask with mask_new: together or not at all)
+static int pose_tick_check(const pa_traj_args* ta, double lambda, const char* who, bool advancing = false) {
   PA_CHECK(ta, "%s: null args", who);
   if (const int rc = pa::robust_check(*ta, who)) return rc;
+  if (advancing) {
+    PA_CHECK(!ta->dt_pair == !ta->dt_new, "%s: dt_pair and dt_new are given together (or both NULL)", who);
+    PA_CHECK(!ta->kp_mask == !ta->mask_new, "%s: kp_mask and mask_new are given together (or both NULL)", who);
+  }
   const int T = ta->T, L = ta->L, K = ta->n_kp;
   // one workgroup per trajectory: correct at any T (the CU count is a performance choice of the
   // caller, StreamingPipeline's fused_pose / split_pose eligibility)
   PA_CHECK(T >= 0 && L >= 2 && L <= pa::GN_CR_LMAX && K >= 0 && K <= pa::GN_KMAX,
            "%s: T %d, L %d (2..%d), n_kp %d (<= %d)", who, T, L, pa::GN_CR_LMAX, K, pa::GN_KMAX);
   if (T == 0) return PA_OK;
+  if (advancing) {
+    PA_CHECK(!ta->dt_pair == !ta->dt_new, "%s: dt_pair and dt_new are given together (or both NULL)", who);
+    PA_CHECK(!ta->kp_mask == !ta->mask_new, "%s: kp_mask and mask_new are given together (or both NULL)", who);
+  }
   PA_CHECK(lambda >= 0.0, "%s: lambda %g < 0", who, lambda);
   PA_CHECK(ta->y && ta->pose && ta->vel && ta->angvel && ta->corners && ta->K && ta->nvalid,
            "%s: null window / model pointer", who);
@@ -234,7 +257,9 @@ static int pose_tick_ws_check(const pa_traj_args* ta, const void* ws, size_t ws_
 
 // advance + linearize (y_new null: the split tick's pre half), with or without a robust noise model
 static void launch_lin(const pa_traj_args* ta, const float* y_new, hipStream_t s) {
-  const auto kernel = ta->robust_proj == PA_ROBUST_NONE ? pa::pose_tick_lin_kernel<false> : pa::pose_tick_lin_kernel<true>;
+  const bool rb = ta->robust_proj != PA_ROBUST_NONE, tm = ta->dt_pair || ta->kp_mask;
+  const auto kernel = tm ? (rb ? pa::pose_tick_lin_kernel<true, true> : pa::pose_tick_lin_kernel<false, true>)
+                         : (rb ? pa::pose_tick_lin_kernel<true, false> : pa::pose_tick_lin_kernel<false, false>);
   hipLaunchKernelGGL(kernel, dim3(ta->T), dim3(64 * pa::TICK_LIN_W), 0, s, *ta, y_new);
 }
 
@@ -258,7 +283,7 @@ static int prior_pair_check(const double* pi, const double* pg, const char* who)
 int pa_window_pose_tick_prior(const pa_traj_args* ta, const float* y_new, double lambda, double* delta, int32_t* info,
                               double* newest_pose, const double* prior_info, const double* prior_grad, void* stream) {
   PA_CHECK(ta && y_new && delta && info, "pose tick: null args / y_new / delta / info");
-  int rc = pose_tick_check(ta, lambda, "pose tick");
+  int rc = pose_tick_check(ta, lambda, "pose tick", true);
   if (rc != PA_OK || ta->T == 0) return rc;
   if ((rc = prior_pair_check(prior_info, prior_grad, "pose tick")) != PA_OK) return rc;
   const int T = ta->T;
@@ -286,7 +311,7 @@ int pa_window_pose_tick(const pa_traj_args* ta, const float* y_new, double lambd
 
 int pa_window_pose_tick_pre_prior(const pa_traj_args* ta, double lambda, void* ws, size_t ws_bytes,
                                   const double* prior_info, const double* prior_grad, void* stream) {
-  int rc = pose_tick_check(ta, lambda, "pose tick pre");
+  int rc = pose_tick_check(ta, lambda, "pose tick pre", true);
   if (rc != PA_OK || ta->T == 0) return rc;
   if ((rc = prior_pair_check(prior_info, prior_grad, "pose tick pre")) != PA_OK) return rc;
   if ((rc = pose_tick_ws_check(ta, ws, ws_bytes, "pose tick pre")) != PA_OK) return rc;
@@ -322,7 +347,9 @@ int pa_window_pose_tick_post(const pa_traj_args* ta, const float* y_new, const v
   if (rc != PA_OK || ta->T == 0) return rc;
   PA_CHECK(y_new && delta && info, "pose tick post: null y_new / delta / info");
   if ((rc = pose_tick_ws_check(ta, ws, ws_bytes, "pose tick post")) != PA_OK) return rc;
-  const auto kernel = ta->robust_proj == PA_ROBUST_NONE ? pa::pose_tick_post_kernel<false> : pa::pose_tick_post_kernel<true>;
+  const bool rb = ta->robust_proj != PA_ROBUST_NONE, tm = ta->kp_mask != nullptr;
+  const auto kernel = tm ? (rb ? pa::pose_tick_post_kernel<true, true> : pa::pose_tick_post_kernel<false, true>)
+                         : (rb ? pa::pose_tick_post_kernel<true, false> : pa::pose_tick_post_kernel<false, false>);
   hipLaunchKernelGGL(kernel, dim3(ta->T), dim3(64 * pa::GN_CR_W), 0, (hipStream_t)stream, *ta, y_new, (const double*)ws,
                      delta, info, newest_pose);
   PA_LAUNCH_CHECK();

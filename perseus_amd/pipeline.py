@@ -43,6 +43,15 @@ def _f64(a, dev, shape=None):
     return t
 
 
+def _mask(a, dev, shape):
+    """Keypoint masks (one bit per keypoint, bit k = keypoint k) as a contiguous int32 device
+    tensor, the 32 bits of each word as given (values up to 2**32 - 1 are taken as unsigned)."""
+    if isinstance(a, torch.Tensor) and a.dtype == torch.int32:
+        return a.to(device=dev).contiguous().reshape(shape)
+    m = np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a).astype(np.int64).astype(np.uint32)
+    return torch.as_tensor(m.view(np.int32), device=dev).contiguous().reshape(shape)
+
+
 def _isig(sigmas, dim, dev):
     if sigmas is None:
         return None
@@ -53,7 +62,7 @@ def _isig(sigmas, dim, dev):
 def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: int, dt: float,
                          vel_frame: str = "world", camera_pose=None, H: int = 256, W: int = 256,
                          proj_sigmas=None, dyn_sigmas=None, cv_sigmas=None, jacobians: bool = True,
-                         nvalid: torch.Tensor | None = None, proj_robust=None):
+                         nvalid: torch.Tensor | None = None, proj_robust=None, dt_pair=None, kp_mask=None):
     """Stage inputs on the device and allocate outputs: returns (args, out).  `args`
     (a pa_traj_args) can be launched repeatedly with `launch(args, device)`; `out`
     holds the output tensors (Jacobians as (n, cols, rows) column-major buffers) and
@@ -63,7 +72,13 @@ def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T
     proj_robust: None, ("huber", k) or ("cauchy", k), k in whitened units: GTSAM's
     noiseModel.Robust on the projection factors (r_proj and j_proj sqrt(w)-scaled, err_proj the
     m-estimator's loss; pa_traj_args.robust_proj); every consumer of the outputs (gn_step,
-    marginals, lm_solve, the streaming ticks) then does IRLS unchanged."""
+    marginals, lm_solve, the streaming ticks) then does IRLS unchanged.
+    dt_pair (optional, (T, L-1) seconds): the dynamics factor of frame pair (l, l+1) of trajectory
+    t uses dt_pair[t, l] instead of dt (pa_traj_args.dt_pair).  kp_mask (optional, (T, L) ints):
+    bit k set = keypoint k of that frame was measured; the projection factors of cleared bits get
+    status 2 and zero residual / Jacobian, as nvalid's (pa_traj_args.kp_mask; K <= 32).  Arrays
+    are staged; a device tensor of the right type (f64 / int32, contiguous) is used in place and
+    read at every launch.  Both are in out["dt_pair"] / out["kp_mask"] and kept alive."""
     if y.device.type != "cuda":
         raise RuntimeError("linearize_trajectories expects the detector output on the GPU (no CPU fallback)")
     if vel_frame not in ("world", "body"):
@@ -104,9 +119,15 @@ def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T
         raise RuntimeError(f"nvalid must be a contiguous int32 ({T},) tensor on {dev}")
     a.nvalid = _lib.ptr(nvalid)
     a.robust_proj, a.robust_proj_k = _lib.robust_code(proj_robust)
+    dtp = None if dt_pair is None else _f64(dt_pair, dev, (T, max(L - 1, 0)))
+    msk = None if kp_mask is None else _mask(kp_mask, dev, (T, L))
+    if msk is not None and nk > 32:
+        raise ValueError(f"kp_mask holds one bit per keypoint: n_kp {nk} > 32")
+    a.dt_pair, a.kp_mask = _lib.ptr(dtp), _lib.ptr(msk)
+    out["dt_pair"], out["kp_mask"] = dtp, msk
     for k in ("r_proj", "err_proj", "status", "r_dyn", "err_dyn", "r_cv", "err_cv", *_JAC):
         setattr(a, k, _lib.ptr(out[k]))
-    out["_keep"] = (y, P, V, Wv, Cn, Kt, Tc, isp, isd, isc, nvalid)  # inputs stay alive until the stream drains
+    out["_keep"] = (y, P, V, Wv, Cn, Kt, Tc, isp, isd, isc, nvalid, dtp, msk)  # inputs stay alive until the stream drains
     return a, out
 
 
@@ -433,7 +454,7 @@ class LMPlan:
 def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: int, dt: float, proj_sigmas, dyn_sigmas,
              cv_sigmas, nvalid: torch.Tensor | None = None, vel_frame: str = "world", camera_pose=None, H: int = 256,
              W: int = 256, newest_pending: bool = False, covariance: bool = False, cov_lambda: float = 1e-9,
-             proj_robust=None, prior=None, **params) -> dict:
+             proj_robust=None, prior=None, dt_pair=None, kp_mask=None, **params) -> dict:
     """Smoothed trajectories: Levenberg-Marquardt over all factors of T trajectories x L frames
     from the keypoints `y` (device) and the initial state, on the device (pa_trajectory_lm_solve;
     layouts as linearize_trajectories, the inputs are not modified).  Returns pose (T*L, 12),
@@ -447,12 +468,15 @@ def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: in
     proj_robust: as prepare_trajectories; the cost is then the sum of the m-estimator's losses and
     the covariance that of the sqrt(w)-weighted system at the final state.
     prior (a PriorPlan): the marginalization prior on frame 0 (LMPlan); its grad / err are updated, and
-    the covariance then has its Lambda in frame 0's block."""
+    the covariance then has its Lambda in frame 0's block.
+    dt_pair, kp_mask: as prepare_trajectories (a frame without any measured keypoint is held by its
+    dynamics factors alone; its rotation is then not observable, see include/perseus_amd.h)."""
     dev = y.device
     P, V, Wv = (_f64(a, dev).clone() for a in (poses, vels, angvels))  # updated in place: never the caller's
     a, lin = prepare_trajectories(y, P, V, Wv, corners, K, T=T, L=L, dt=dt, vel_frame=vel_frame,
                                   camera_pose=camera_pose, H=H, W=W, proj_sigmas=proj_sigmas, dyn_sigmas=dyn_sigmas,
-                                  cv_sigmas=cv_sigmas, nvalid=nvalid, proj_robust=proj_robust)
+                                  cv_sigmas=cv_sigmas, nvalid=nvalid, proj_robust=proj_robust, dt_pair=dt_pair,
+                                  kp_mask=kp_mask)
     P, V, Wv = lin["_keep"][1:4]
     plan = LMPlan(a, lin, T=T, L=L, newest_pending=newest_pending, prior=prior, **params)
     plan.launch()
@@ -466,14 +490,28 @@ def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: in
 
 
 def window_advance(y_new: torch.Tensor, win: dict, *, dt: float, vel_frame: str = "world",
-                   nvalid: torch.Tensor | None = None) -> None:
+                   nvalid: torch.Tensor | None = None, dt_new=None, mask_new=None) -> None:
     """pa_window_advance on the device's current stream: every trajectory's window
     (win: y (T, L, 2K) f32, pose (T, L, 12), angvel / vel (T, L, 3) f64) moves one frame,
     y_new (T, 2K) becomes its last frame, whose pose is predicted by the
     PoseDynamicsFactor model (factors.py:100-105).  nvalid (optional, int32 (T,)): the
-    window's count of real frames, += 1 up to L (pa_window_advance_n)."""
+    window's count of real frames, += 1 up to L (pa_window_advance_n).
+    dt_new (f64 (T,) device tensor or address): the window carries per-pair periods in win["dt"]
+    (T, L-1) f64; they move with it, dt_new[t] becomes the new last pair's and predicts the new
+    frame.  mask_new (int32 (T,) device tensor or address): the same for the keypoint masks
+    win["mask"] (T, L) int32 (pa_window_advance_t; either ring alone is fine)."""
     T, L, ny = win["y"].shape
     dev = win["y"].device
+    if dt_new is not None or mask_new is not None:
+        if (dt_new is None) != (win.get("dt") is None) or (mask_new is None) != (win.get("mask") is None):
+            raise ValueError("window_advance: dt_new goes with win['dt'] and mask_new with win['mask']")
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().pa_window_advance_t(
+                T, L, ny // 2, y_new.data_ptr(), win["y"].data_ptr(), win["pose"].data_ptr(),
+                win["angvel"].data_ptr(), win["vel"].data_ptr(), _lib.ptr(nvalid), _lib.ptr(win.get("dt")),
+                _lib.ptr(win.get("mask")), _lib.ptr(dt_new), _lib.ptr(mask_new), float(dt),
+                _lib.VEL_WORLD if vel_frame == "world" else _lib.VEL_BODY, _lib.stream_of(dev)), "pa_window_advance_t")
+        return
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().pa_window_advance_n(
             T, L, ny // 2, y_new.data_ptr(), win["y"].data_ptr(), win["pose"].data_ptr(), win["angvel"].data_ptr(),

@@ -235,12 +235,13 @@ def _isig(noise, dim, device):
 
 
 # ---------------------------------------------------------- batched fast path
-def linearize_dynamics(T1, w, v, T2, dt: float, vel_frame: str = "world", inv_sigma=None, jacobians=True):
+def linearize_dynamics(T1, w, v, T2, dt, vel_frame: str = "world", inv_sigma=None, jacobians=True):
     """Batched PoseDynamicsFactor (factors.py:54-142) on the GPU.
 
     T1, T2 (n,12) poses; w, v (n,3).  Returns dict of device tensors r (n,6), J0 (n,6,6),
     J1 (n,6,3), J2 (n,6,3), J3 (n,6,6) (row-major views of the column-major buffers)
-    and err (n,) when inv_sigma is given (whitened outputs)."""
+    and err (n,) when inv_sigma is given (whitened outputs).  dt: seconds, one scalar for every
+    factor or a length-n array, one per factor (pa_dyn_linearize_dt)."""
     assert vel_frame in ["world", "body"], "vel_frame must be 'world' or 'body'."
     dev = _device()
     T1, w, v, T2 = (_dev(a, dev) for a in (T1, w, v, T2))
@@ -249,10 +250,17 @@ def linearize_dynamics(T1, w, v, T2, dt: float, vel_frame: str = "world", inv_si
     r = torch.empty((n, 6), dtype=torch.float64, device=dev)
     J = [torch.empty((n, c, 6), dtype=torch.float64, device=dev) for c in (6, 3, 3, 6)] if jacobians else [None] * 4
     err = torch.empty(n, dtype=torch.float64, device=dev) if isg is not None else None
-    _lib.check(_lib.lib().pa_dyn_linearize(
-        n, T1.data_ptr(), w.data_ptr(), v.data_ptr(), T2.data_ptr(), float(dt),
-        _lib.VEL_WORLD if vel_frame == "world" else _lib.VEL_BODY, _lib.ptr(isg), r.data_ptr(),
-        *[_lib.ptr(j) for j in J], _lib.ptr(err), _lib.stream_of(dev)), "pa_dyn_linearize")
+    tail = (_lib.VEL_WORLD if vel_frame == "world" else _lib.VEL_BODY, _lib.ptr(isg), r.data_ptr(),
+            *[_lib.ptr(j) for j in J], _lib.ptr(err), _lib.stream_of(dev))
+    if (dt.dim() if isinstance(dt, torch.Tensor) else np.ndim(dt)) == 0:
+        _lib.check(_lib.lib().pa_dyn_linearize(n, T1.data_ptr(), w.data_ptr(), v.data_ptr(), T2.data_ptr(), float(dt),
+                                               *tail), "pa_dyn_linearize")
+    else:  # one dt per factor
+        dts = _dev(dt, dev).reshape(-1)
+        if dts.numel() != n:
+            raise ValueError(f"dt must be a scalar or hold one value per factor ({n}), got {dts.numel()}")
+        _lib.check(_lib.lib().pa_dyn_linearize_dt(n, T1.data_ptr(), w.data_ptr(), v.data_ptr(), T2.data_ptr(),
+                                                  dts.data_ptr(), *tail), "pa_dyn_linearize_dt")
     out = {"r": r, "err": err}
     if jacobians:
         for i, j in enumerate(J):

@@ -69,7 +69,16 @@ class StreamingPipeline:
     pa_window_marginalize with the tick's delta and info.  self.prior.minfo (device, int32) is 2
     until the window has filled, then 0.  Not with pre_ahead (between ticks the factor outputs
     already belong to the next tick): ValueError.  solve_window(with_prior=True) is the
-    Levenberg-Marquardt solve of such a window with its prior; without the keyword it raises."""
+    Levenberg-Marquardt solve of such a window with its prior; without the keyword it raises.
+    timed=True: real timestamps (cameras skip frames, so consecutive frames are 1, 2 or 3 periods
+    apart; one of the batched cameras has no frame; a hand hides single corners).  The window
+    carries two rings beside its frames, self.win["dt"] (n, L-1) f64, the period of every frame
+    pair (initially dt), and self.win["mask"] (n, L) int32, one bit per keypoint (initially all
+    ones); pa_traj_args.dt_pair / kp_mask point at them, so every factor, solve_window() and
+    window_covariance() use them.  tick() / tick_keypoints() take stamps=, present= and kp_mask=;
+    the new pair's dt and the new frame's mask go through one small pinned block [dt_new (n) f64 |
+    mask_new (n) u32] that the graph copies to the device on the stream that runs the advance
+    (zero_copy: read in place), so one captured graph serves every tick.  Not with pre_ahead."""
 
     def __init__(self, model, n_cams: int = 3, src_hw=(720, 1280), bgr: bool = True, host_crop: bool = True,
                  graph: bool = True, near: float | None = None, far: float | None = None, device=None,
@@ -77,9 +86,16 @@ class StreamingPipeline:
                  proj_sigma: float = 1.0, dyn_sigma: float = 0.1, cv_sigma: float = 0.1, lam: float = 1e-2,
                  init_pose=None, init_vel=None, init_angvel=None, split_k: bool = True,
                  zero_copy: bool | None = None, split_pose: bool = True, pre_ahead: bool = False,
-                 zero_copy_out: bool = True, proj_robust=None, marginalize: bool = False):
+                 zero_copy_out: bool = True, proj_robust=None, marginalize: bool = False, timed: bool = False):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingPipeline needs a ROCm GPU (no CPU fallback)")
+        if timed and pre_ahead:
+            raise ValueError("StreamingPipeline: timed=True cannot run with pre_ahead=True (the next tick's dt is "
+                             "not known when its pre half runs)")
+        if timed and not pose_window:
+            raise ValueError("StreamingPipeline: timed=True needs the pose stage (pose_window > 0)")
+        self.timed = bool(timed)
+        self._timing_staged = False
         if marginalize and pre_ahead:
             raise ValueError("StreamingPipeline: marginalize=True cannot run with pre_ahead=True (between ticks the "
                              "factor outputs already belong to the next tick)")
@@ -260,7 +276,14 @@ class StreamingPipeline:
                                    delta=self.gn.out["delta"], gn_info=info, nvalid=self.nvalid,
                                    n_kp=self.model.n_keypoints)
 
+    def _enqueue_timed_in(self):
+        """timed: this tick's [dt_new | mask_new] to the device, on the stream that runs the advance
+        and before it (one 12 n byte copy; zero_copy: nothing, the advance reads the pinned block)."""
+        if self.timed and not self.zero_copy:
+            self.tm_d.copy_(self.tm_h, non_blocking=True)
+
     def _enqueue_pose_pre(self):
+        self._enqueue_timed_in()
         self._enqueue_prior_in()
         pipeline.window_pose_tick_pre(self.traj_args, self.tick_ws, lam=self.gn.lam, prior=self.prior)
 
@@ -283,12 +306,14 @@ class StreamingPipeline:
                 self._enqueue_pose_pre()
             self._enqueue_pose_post()
             return
+        self._enqueue_timed_in()
         self._enqueue_prior_in()
         if self.fused_pose:
             pipeline.window_pose_tick(self.traj_args, self.y, lam=self.gn.lam, delta=self.gn.out["delta"],
                                       info=self.gn.out["info"], newest=self.pose_d, prior=self.prior)
         else:
-            pipeline.window_advance(self.y, self.win, dt=self.dt, vel_frame=self.vel_frame, nvalid=self.nvalid)
+            tm = dict(dt_new=self._tm_ptrs[0], mask_new=self._tm_ptrs[1]) if self.timed else {}
+            pipeline.window_advance(self.y, self.win, dt=self.dt, vel_frame=self.vel_frame, nvalid=self.nvalid, **tm)
             pipeline.launch(self.traj_args, self.dev)
             self.gn.launch()  # delta, and info straight into the output block
             pipeline.window_retract(self.win, self.gn.out["delta"], self.gn.out["info"], newest=self.pose_d)
@@ -317,13 +342,38 @@ class StreamingPipeline:
         # real frames per camera window (from its end): until L ticks have run, the frames
         # before them are the initial state with no measurement, and carry no projection factor
         self.nvalid = torch.zeros(n, dtype=torch.int32, device=dev)
+        rings = {}
+        if self.timed:
+            # the rings, and the tick's [dt_new (n) f64 | mask_new (n) u32] block: pinned, and its
+            # device copy (zero_copy: the advance reads the pinned block in place)
+            self.win["dt"] = torch.full((n, Lw - 1), self.dt, **f64)
+            self.win["mask"] = torch.full((n, Lw), -1, dtype=torch.int32, device=dev)
+            rings = dict(dt_pair=self.win["dt"], kp_mask=self.win["mask"])
+            self.tm_h = torch.zeros(n * 12, dtype=torch.uint8).pin_memory()
+            self.tm_d = torch.zeros(n * 12, dtype=torch.uint8, device=dev)
+            self.dt_new_h = self.tm_h[:n * 8].view(torch.float64)
+            self.mask_new_h = self.tm_h[n * 8:].view(torch.int32)
+            self.dt_new_h.fill_(self.dt)
+            self.mask_new_h.fill_(-1)
+            self._stamps = None  # the last tick's stamps (None: the next tick uses the nominal dt)
         self.traj_args, self.lin = pipeline.prepare_trajectories(
             self.win["y"].view(n * Lw, 2 * nk), self.win["pose"].view(n * Lw, 12), self.win["vel"].view(n * Lw, 3),
             self.win["angvel"].view(n * Lw, 3), corners, K, T=n, L=Lw, dt=self.dt, vel_frame=vel_frame, H=self.H,
             W=self.W, proj_sigmas=[proj_sigma] * 2, dyn_sigmas=[dyn_sigma] * 6, cv_sigmas=[cv_sigma] * 3,
-            nvalid=self.nvalid, proj_robust=proj_robust)
+            nvalid=self.nvalid, proj_robust=proj_robust, **rings)
         for k in ("y", "pose", "vel", "angvel"):  # linearize reads the window in place, no staging copy
             assert self.lin["_keep"][("y", "pose", "vel", "angvel").index(k)].data_ptr() == self.win[k].data_ptr()
+        if self.timed:
+            assert self.traj_args.dt_pair == self.win["dt"].data_ptr()
+            assert self.traj_args.kp_mask == self.win["mask"].data_ptr()
+            base = self.tm_d.data_ptr()
+            if self.zero_copy:
+                dp = C.c_void_p()
+                _lib.check(_lib.lib().pa_host_device_pointer(C.c_void_p(self.tm_h.data_ptr()), C.byref(dp)),
+                           "host_device_pointer")
+                base = dp.value
+            self._tm_ptrs = (base, base + n * 8)
+            self.traj_args.dt_new, self.traj_args.mask_new = self._tm_ptrs
         if self.marginalize:
             # the prior on frame 0: the fused / split ticks get it beside the pa_traj_args (the _prior
             # entry points), the four-launch path's GN step from the plan
@@ -359,6 +409,10 @@ class StreamingPipeline:
         with torch.cuda.stream(self.stream):
             self.win["y"].zero_()
             self.nvalid.zero_()
+            if self.timed:  # the rings back to the nominal dt and all measured; the last stamps forgotten
+                self.win["dt"].fill_(self.dt)
+                self.win["mask"].fill_(-1)
+                self._stamps = None
             if self.prior is not None:
                 self.prior.zero()
             for k in ("pose", "vel", "angvel"):
@@ -492,7 +546,14 @@ class StreamingPipeline:
             self._enqueue_pose_pre()
 
     def run(self) -> np.ndarray:
-        """Process the staged tick; returns a copy of the (n, K, 2) pixel coordinates."""
+        """Process the staged tick; returns a copy of the (n, K, 2) pixel coordinates.
+        timed: called without tick() having staged this tick's timing (run() or pipe(rgb, depth)
+        directly), the tick takes the nominal dt and all keypoints measured, and the last stamps
+        move on by dt, as tick() without keywords.  (replay() alone stages nothing: it runs
+        whatever dt_new / mask_new the pinned block holds.)"""
+        if self.timed and not self._timing_staged:
+            self._stage_timing(None, None, None)
+        self._timing_staged = False  # (this tick's; the next one stages its own)
         with torch.cuda.stream(self.stream):  # replay() launches on the current stream
             self.replay()
         if self.pre_ahead:
@@ -505,9 +566,42 @@ class StreamingPipeline:
         self.stage(rgb, depth)
         return self.run()
 
-    def tick(self, rgb: np.ndarray, depth: np.ndarray | None = None):
+    def _stage_timing(self, stamps, present, kp_mask) -> None:
+        """timed: this tick's dt_new / mask_new into the pinned block (before anything else of the
+        tick is staged or enqueued: a bad stamp raises ValueError and leaves the window untouched).
+        stamps (n,) seconds per camera: dt_new = stamps - the previous tick's (the first tick after
+        construction or a reset: the nominal dt); None: the nominal dt.  present (n,) bool: an absent
+        camera gets mask 0 (its window still advances to its stamp, on the prediction alone; whatever
+        its slot of the batch holds is run and ignored).  kp_mask (n,) ints, one bit per keypoint,
+        ANDed with present.  All None: nominal dt, all measured."""
+        if not self.timed:
+            if stamps is not None or present is not None or kp_mask is not None:
+                raise ValueError("stamps / present / kp_mask need a pipeline built with timed=True")
+            return
+        n = self.n
+        s = None if stamps is None else np.asarray(stamps, np.float64).reshape(n)
+        if s is None or self._stamps is None:
+            dt_new = np.full(n, self.dt)
+            if s is not None and not np.isfinite(s).all():
+                raise ValueError(f"stamps must be finite, got {s}")
+        else:
+            dt_new = s - self._stamps
+            if not (np.isfinite(dt_new).all() and (dt_new > 0).all()):
+                raise ValueError(f"stamps must increase by a positive finite dt per camera, got dt {dt_new}")
+        mask = np.full(n, 0xFFFFFFFF, np.int64)
+        if kp_mask is not None:
+            mask &= np.asarray(kp_mask).astype(np.int64).reshape(n)
+        if present is not None:
+            mask[~np.asarray(present, bool).reshape(n)] = 0
+        self.dt_new_h.numpy()[:] = dt_new
+        self.mask_new_h.numpy()[:] = mask.astype(np.uint32).view(np.int32)
+        self._stamps = s if s is not None else (None if self._stamps is None else self._stamps + self.dt)
+        self._timing_staged = True  # (run() stages the nominal timing itself when a caller skipped this)
+
+    def tick(self, rgb: np.ndarray, depth: np.ndarray | None = None, *, stamps=None, present=None, kp_mask=None):
         """One camera tick through the pose stage: (pixels (n, K, 2), newest pose of each
         camera's window (n, 12: R row-major, t), GN info (n,) int32, 0 = solved).
+        stamps / present / kp_mask (timed=True only): see _stage_timing.
 
         The results are read from the pinned output block (self.px_h / pose_h / info_h), the
         only place every tick form writes them.  With pre_ahead, the next tick's pre half has
@@ -516,10 +610,11 @@ class StreamingPipeline:
         advanced window, not this tick's (window_state() says the same)."""
         if not self.pose_L:
             raise RuntimeError("tick() needs the pose stage (pose_window > 0)")
+        self._stage_timing(stamps, present, kp_mask)
         px = self(rgb, depth)
         return px, self.pose_h.numpy().copy(), self.info_h.numpy().copy()
 
-    def tick_keypoints(self, y) -> tuple:
+    def tick_keypoints(self, y, *, stamps=None, present=None, kp_mask=None) -> tuple:
         """The pose stage alone on given normalized keypoints y (n, 2K) (the detector's output
         convention, validate.py:139-141): the same launches as a tick's pose stage, from
         self.y, captured as their own graph when graph=True.  Returns (newest pose (n, 12),
@@ -528,6 +623,8 @@ class StreamingPipeline:
         already hold the next tick's pre half."""
         if not self.pose_L:
             raise RuntimeError("tick_keypoints() needs the pose stage (pose_window > 0)")
+        self._stage_timing(stamps, present, kp_mask)
+        self._timing_staged = False  # (consumed by this tick, which does not go through run())
         self.y_h.numpy()[:] = np.asarray(y, np.float32).reshape(self.y_h.shape)
 
         def enqueue():
