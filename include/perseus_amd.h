@@ -276,13 +276,29 @@ int pa_cv_linearize(int n, const double* v1_dev, const double* v2_dev, const dou
  *     given the same dt_pair / kp_mask pointers as the pre half).  On the newest frame of a pre
  *     half the order of statuses is unchanged: the mask gives 2, the pre half then stamps 3 on
  *     all of that frame, and the post half re-evaluates with the mask.
+ * isig_cw / r_cw / err_cw: the ConstantVelocityFactor on the ANGULAR velocity ("cw"; the reference's
+ * factor, factors.py:145-171, is generic in its keys and GTSAM users put it on the angular-velocity
+ * keys as well): per pair (l, l+1) of trajectory t, r = (angvel[l+1] - angvel[l]) * isig_cw, with the
+ * constant Jacobians -diag(isig_cw) and +diag(isig_cw) (not written) and no dt scaling, also with
+ * dt_pair.  r_cw != NULL switches it on, for every pair whatever nvalid, kp_mask or the statuses
+ * say (as the factor on the linear velocity); a zero-initialised triple means off, and off is the
+ * kernels and the bits from before the fields existed.  err_cw may be NULL; isig_cw NULL means
+ * unwhitened in pa_trajectory_linearize only.  Every entry point that takes a pa_traj_args honours
+ * it: the four LM solves (they require isig_cw and err_cw once it is on; err_cw's entries enter the
+ * cost's fixed-order sum right after err_cv's) and pa_window_pose_tick with its _pre / _post /
+ * _reduce / _prior forms (isig_cw required; the factor needs no keypoints, so the pre half has the
+ * newest pair's).  Inconsistent fields return PA_EINVAL before any launch, after every older check.
+ * The entry points with explicit pointer lists have the siblings pa_trajectory_gn_step_cw,
+ * pa_trajectory_marginals_cw and pa_window_marginalize_cw below.
  * A frame without any measured keypoint is held by its two dynamics factors and the constant-
- * velocity factors alone.  Its rotation is then NOT observable from this factor set: nothing
- * couples successive angular velocities (ConstantVelocityFactor is on the linear velocity only),
- * so frame l's rotation and the angular velocities of frames l-1 and l can move together at no
- * cost: 9 equations for the frame's 12 unknowns.  Such a frame needs a lambda of the streaming
- * tick's order (1e-2), exactly as a partly filled window does (see pa_trajectory_marginals); the
- * tick then holds it at its prediction.  pa_trajectory_gn_step, pa_trajectory_marginals and
+ * velocity factors alone.  WITHOUT the factor on the angular velocity its rotation is NOT
+ * observable: nothing couples successive angular velocities, so frame l's rotation and the angular
+ * velocities of frames l-1 and l can move together at no cost: 9 equations for the frame's 12
+ * unknowns.  Such a frame then needs a lambda of the streaming tick's order (1e-2), exactly as a
+ * partly filled window does (see pa_trajectory_marginals); the tick holds it at its prediction.
+ * WITH the factor the three missing equations are there: the frame's rotation is observable through
+ * its neighbours' (12 equations), its marginal covariance is finite at lambda -> 0, and partly filled
+ * or timed windows no longer lean on the damping.  pa_trajectory_gn_step, pa_trajectory_marginals and
  * pa_window_marginalize consume statuses and factor outputs only and need nothing else. */
 typedef struct pa_traj_args {
   int T, L, n_kp, H, W;
@@ -298,9 +314,14 @@ typedef struct pa_traj_args {
   const double* isig_proj; /* (2) or NULL */
   const double* isig_dyn;  /* (6) or NULL */
   const double* isig_cv;   /* (3) or NULL */
+  const double* isig_cw;   /* (3) or NULL: the angular-velocity factor's whitening (see r_cw) */
   double *r_proj, *j_proj, *err_proj;
   int32_t* status;
   double *r_dyn, *j_dyn0, *j_dyn1, *j_dyn2, *j_dyn3, *err_dyn;
+  /* the constant-velocity factor on the ANGULAR velocity ("cw"; r_cw NULL = off: every kernel and
+   * output bit is then what it was before the field existed).  r_cw (T*(L-1), 3), err_cw (T*(L-1))
+   * or NULL; its Jacobians are the constants -+ diag(isig_cw) and are not written. */
+  double *r_cw, *err_cw;
   double *r_cv, *j_cv0, *j_cv1, *err_cv;
   /* real timestamps (all four NULL = none: every kernel, output bit and captured graph is then what
    * it was before these fields existed).  They stand before nvalid, not at the struct's end: the
@@ -353,12 +374,15 @@ int pa_trajectory_gn_step(int T, int L, int n_kp, const double* r_proj, const do
  * at least one of cov / cov_newest.  Every block is exactly symmetric.  info (T, required) = 0
  * or the 1-based frame whose pivot block of the top-down block elimination was not positive
  * definite; every output block of that trajectory is then NaN.
- * lambda = 0 has no special case: on a full window the last frame's angular velocity is in no
- * factor, so lambda = 0 fails at frame L (as pa_trajectory_gn_step does); pass a small lambda
- * (for example 1e-9) for the undamped Gauss-Newton covariance -- the unconstrained variable
- * is decoupled and gets variance 1 / lambda.  Partly filled windows (nvalid < L) and a pending
- * newest frame (status 3) are singular at lambda = 0 for a real reason (9 equations for 12
- * unknowns per frame without keypoints) and need a lambda of the streaming tick's order (1e-2).
+ * lambda = 0 has no special case.  Without the factor on the angular velocity (pa_traj_args.r_cw,
+ * the _cw sibling below) the last frame's angular velocity of a full window is in no factor, so
+ * lambda = 0 fails at frame L (as pa_trajectory_gn_step does); pass a small lambda (for example
+ * 1e-9) for the undamped Gauss-Newton covariance -- the unconstrained variable is decoupled and
+ * gets variance 1 / lambda.  Partly filled windows (nvalid < L) and a pending newest frame (status
+ * 3) are then singular at lambda = 0 for a real reason (9 equations for 12 unknowns per frame
+ * without keypoints) and need a lambda of the streaming tick's order (1e-2).  With the factor every
+ * angular velocity is in a factor: lambda = 0 solves a full window (info 0), and frames without
+ * keypoints between measured ones have finite variances at lambda -> 0.
  * T >= 0 (0 is a no-op), L >= 2, 0 <= n_kp <= 16; everything else returns PA_EINVAL before any
  * launch.  One launch on `stream`, no host synchronisation (capturable).
  * ws: pa_trajectory_marginals_workspace bytes. */
@@ -372,11 +396,13 @@ int pa_trajectory_marginals(int T, int L, int n_kp, const double* r_proj, const 
 /* Levenberg-Marquardt over the same graph (what GTSAM's LevenbergMarquardtOptimizer::optimize
  * does on the host for the reference's users), per trajectory and independently, all on the
  * device: 1 + 2 max_iters launches on `stream`, no host synchronisation (capturable).
- * args: the pa_traj_args of pa_trajectory_linearize; all three isig_* are required (the cost is
- * defined on whitened residuals), as is every factor output and Jacobian pointer; n_kp >= 1;
+ * args: the pa_traj_args of pa_trajectory_linearize; isig_proj, isig_dyn and isig_cv are required
+ * (the cost is defined on whitened residuals), as is every factor output and Jacobian pointer (r_cw,
+ * err_cw and isig_cw only together, as the switch of the factor on the angular velocity); n_kp >= 1;
  * nvalid is honoured.  args->pose / vel / angvel are updated IN PLACE to the final accepted
  * state, and on return the factor outputs hold the linearization at that state.
- *   1. C = sum of err (0.5 |r_w|^2) over the dynamics and constant-velocity factors and the
+ *   1. C = sum of err (0.5 |r_w|^2) over the dynamics and constant-velocity factors (with r_cw: those
+ *      on the angular velocity too, right after the ones on the linear velocity) and the
  *      projection factors with status 0 at the state x (with args->robust_proj their err is the
  *      m-estimator's rho, so C is the robust cost); lambda = lambda0; cost0 = cost_hist[0] = C.
  *   2. iteration k = 1..max_iters: (J^T J + lambda I) delta = -J^T r (pa_trajectory_gn_step's
@@ -497,8 +523,9 @@ int pa_window_pose_tick_reduce(const pa_traj_args* args, double lambda, void* ws
  * prior on the state that is now oldest (a LinearContainerFactor with its linearization point),
  * instead of pa_window_advance simply forgetting frame 0.
  * The prior is held per trajectory, f64, on the device, in INFORMATION form (the marginal is only
- * positive semi-definite -- frame 1's angular velocity gets no information from frame 0 -- so a
- * square root would not exist):
+ * positive semi-definite -- without the factor on the angular velocity (pa_window_marginalize_cw)
+ * frame 1's angular velocity gets no information from frame 0; with it, it gets the factor's --
+ * so the form that always exists is kept):
  *   info (T, 12, 12) row-major, the symmetric Lambda over the frame block [pose tangent 6 |
  *   angvel 3 | vel 3] in pa_window_retract's chart;  eta (T, 12);  xbar_pose (T, 12), xbar_angvel
  *   (T, 3), xbar_vel (T, 3): the state it was linearized at.
@@ -566,6 +593,36 @@ int pa_trajectory_marginals_prior(int T, int L, int n_kp, const double* r_proj, 
                                   double* cov, double* cross, double* cov_newest, int32_t* info, void* ws,
                                   size_t ws_bytes, const double* prior_info, const double* prior_grad,
                                   void* stream);
+/* The same three with the ConstantVelocityFactor on the angular velocity (pa_traj_args.r_cw): the
+ * _prior argument lists plus r_cw (T*(L-1), 3), the factor's WHITENED residuals as
+ * pa_trajectory_linearize writes them, and isig_cw (3), its whitening (required with r_cw: the
+ * Jacobians are -+ diag(isig_cw)), both before lambda.  The factor has constant Jacobians, so it is
+ * folded into the blocks in closed form: per pair touching frame l, D_l[6+i][6+i] += isig_cw_i^2,
+ * E_l[6+i][6+i] -= isig_cw_i^2 and g_l[6+i] += isig_cw_i (r_{l-1,i} - r_{l,i}) (a term left out at
+ * the window's ends); for pa_window_marginalize_cw, F = B^T B and h = B^T r gain the pair (0, 1)'s
+ * frame-1 part.  Prior pointers both NULL: no prior.  r_cw NULL: the _prior parent (for
+ * pa_window_marginalize_cw: pa_window_marginalize), bit for bit.  Workspace sizes: the parents'. */
+int pa_trajectory_gn_step_cw(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                             const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                             const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
+                             const double* j_cv0, const double* j_cv1, const double* r_cw, const double* isig_cw,
+                             double lambda, double* D, double* E, double* g, double* delta, int32_t* info, void* ws,
+                             size_t ws_bytes, const double* prior_info, const double* prior_grad, void* stream);
+int pa_trajectory_marginals_cw(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                               const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                               const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
+                               const double* j_cv0, const double* j_cv1, const double* r_cw, const double* isig_cw,
+                               double lambda, double* cov, double* cross, double* cov_newest, int32_t* info, void* ws,
+                               size_t ws_bytes, const double* prior_info, const double* prior_grad, void* stream);
+int pa_window_marginalize_cw(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                             const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                             const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
+                             const double* j_cv0, const double* j_cv1, const double* prior_info_in,
+                             const double* prior_grad_in, const double* r_cw, const double* isig_cw, double lambda,
+                             const double* delta, const int32_t* gn_info, const int32_t* nvalid, const double* pose,
+                             const double* angvel, const double* vel, double* info_out, double* eta_out,
+                             double* xbar_pose_out, double* xbar_angvel_out, double* xbar_vel_out, int32_t* minfo,
+                             void* stream);
 int pa_window_pose_tick_prior(const pa_traj_args* args, const float* y_new_dev, double lambda, double* delta_dev,
                               int32_t* info_dev, double* newest_pose_dev, const double* prior_info,
                               const double* prior_grad, void* stream);

@@ -28,9 +28,11 @@ class TrajArgs(C.Structure):
                 ("y", C.c_void_p), ("pose", C.c_void_p), ("vel", C.c_void_p), ("angvel", C.c_void_p),
                 ("corners", C.c_void_p), ("K", C.c_void_p), ("tcam", C.c_void_p), ("dt", C.c_double),
                 ("vel_frame", C.c_int), ("isig_proj", C.c_void_p), ("isig_dyn", C.c_void_p),
-                ("isig_cv", C.c_void_p), ("r_proj", C.c_void_p), ("j_proj", C.c_void_p), ("err_proj", C.c_void_p),
+                ("isig_cv", C.c_void_p), ("isig_cw", C.c_void_p),
+                ("r_proj", C.c_void_p), ("j_proj", C.c_void_p), ("err_proj", C.c_void_p),
                 ("status", C.c_void_p), ("r_dyn", C.c_void_p), ("j_dyn0", C.c_void_p), ("j_dyn1", C.c_void_p),
-                ("j_dyn2", C.c_void_p), ("j_dyn3", C.c_void_p), ("err_dyn", C.c_void_p), ("r_cv", C.c_void_p),
+                ("j_dyn2", C.c_void_p), ("j_dyn3", C.c_void_p), ("err_dyn", C.c_void_p),
+                ("r_cw", C.c_void_p), ("err_cw", C.c_void_p), ("r_cv", C.c_void_p),
                 ("j_cv0", C.c_void_p), ("j_cv1", C.c_void_p), ("err_cv", C.c_void_p),
                 ("dt_pair", C.c_void_p), ("kp_mask", C.c_void_p), ("dt_new", C.c_void_p), ("mask_new", C.c_void_p),
                 ("nvalid", C.c_void_p), ("robust_proj", C.c_int), ("robust_proj_k", C.c_double)]
@@ -130,6 +132,13 @@ _SIGS = {
                                     + [C.c_void_p] * 6 + [C.c_size_t] + [C.c_void_p] * 3),
     "pa_trajectory_marginals_prior": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_double]
                                       + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 3),
+    # the _prior siblings plus r_cw, isig_cw before lambda (the factor on the angular velocity)
+    "pa_trajectory_gn_step_cw": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13 + [C.c_double]
+                                 + [C.c_void_p] * 6 + [C.c_size_t] + [C.c_void_p] * 3),
+    "pa_trajectory_marginals_cw": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13 + [C.c_double]
+                                   + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 3),
+    "pa_window_marginalize_cw": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 15 + [C.c_double]
+                                 + [C.c_void_p] * 13),
     "pa_window_pose_tick_prior": (C.c_int, [C.POINTER(TrajArgs), C.c_void_p, C.c_double] + [C.c_void_p] * 6),
     "pa_window_pose_tick_pre_prior": (C.c_int, [C.POINTER(TrajArgs), C.c_double, C.c_void_p, C.c_size_t]
                                       + [C.c_void_p] * 3),

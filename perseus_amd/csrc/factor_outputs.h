@@ -1,9 +1,9 @@
 // The factor outputs of pa_trajectory_linearize (the output pointers of pa_traj_args,
 // include/perseus_amd.h), listed once: X(field, element type, elements per unit, unit), the unit
 // a projection (T*L*K of them) or a frame pair (T*(L-1)).  Everything that treats them as a set
-// -- the struct of the 14 pointers, the select between two sets, the T = 1 view of one
-// trajectory, the LM workspace's copy of the set with its null checks and its final copy
-// (lm.hip) -- expands this list, so a new output is added here (and to the public header and
+// -- the struct of the pointers, the T = 1 view of one trajectory, the LM workspace's copy of
+// the set with its select between the two, its null checks and its final copy (lm.hip) --
+// expands this list, so a new output is added here (and to the public header and
 // _lib.py).  Every expansion is unrolled by the preprocessor: no table is indexed at run time.
 #pragma once
 #include <cmath>
@@ -25,6 +25,14 @@
   X(j_cv0, double, 9, FU_PAIR)     \
   X(j_cv1, double, 9, FU_PAIR)     \
   X(err_cv, double, 1, FU_PAIR)
+// The optional outputs: those of the constant-velocity factor on the angular velocity ("cw",
+// pa_traj_args.r_cw; null = the factor is off).  Every expansion that only carries pointers takes
+// both lists (PA_FACTOR_OUTPUTS_ALL); the LM solve's null checks take the required list alone, and
+// it keeps this pair beside its two sets (LmDev, lm.hip) and copies it under the switch.
+#define PA_FACTOR_OUTPUTS_CW(X) \
+  X(r_cw, double, 3, FU_PAIR)   \
+  X(err_cw, double, 1, FU_PAIR)
+#define PA_FACTOR_OUTPUTS_ALL(X) PA_FACTOR_OUTPUTS(X) PA_FACTOR_OUTPUTS_CW(X)
 
 namespace pa {
 
@@ -49,9 +57,16 @@ __host__ __device__ constexpr N factor_units(FactorUnit u, N np, N nd) {
   return u == FU_PROJ ? np : nd;
 }
 
-struct FactorSet {
+// the required outputs alone (lm.hip keeps its two sets in this form, the layout they had before
+// the optional pair existed, and the pair beside them)
+struct FactorSetReq {
 #define PA_X(f, V, n, u) V* f;
   PA_FACTOR_OUTPUTS(PA_X)
+#undef PA_X
+};
+struct FactorSet : FactorSetReq {
+#define PA_X(f, V, n, u) V* f;
+  PA_FACTOR_OUTPUTS_CW(PA_X)
 #undef PA_X
 };
 
@@ -59,17 +74,7 @@ struct FactorSet {
 __host__ __device__ __forceinline__ FactorSet factor_set(const pa_traj_args& ta) {
   FactorSet s;
 #define PA_X(f, V, n, u) s.f = ta.f;
-  PA_FACTOR_OUTPUTS(PA_X)
-#undef PA_X
-  return s;
-}
-
-// b if w, else a: per pointer a select between two kernel-argument structs (uniform when w
-// is; an indexed copy, sets[w], would put both sets in scratch)
-__device__ __forceinline__ FactorSet factor_set_select(const FactorSet& a, const FactorSet& b, bool w) {
-  FactorSet s;
-#define PA_X(f, V, n, u) s.f = w ? b.f : a.f;
-  PA_FACTOR_OUTPUTS(PA_X)
+  PA_FACTOR_OUTPUTS_ALL(PA_X)
 #undef PA_X
   return s;
 }
@@ -92,6 +97,11 @@ __device__ __forceinline__ pa_traj_args traj_view(const pa_traj_args& ta, int t,
   a1.angvel = ta.angvel + f0 * 3;
 #define PA_X(f, V, n, u) a1.f = NULLS ? off(s.f, factor_units(u, p0, d0) * n) : s.f + factor_units(u, p0, d0) * n;
   PA_FACTOR_OUTPUTS(PA_X)
+#undef PA_X
+  // the optional pair keeps its nulls whatever NULLS says: r_cw null is the factor's switch
+  // (read only by the CW instantiations, factors_dev.h)
+#define PA_X(f, V, n, u) a1.f = off(s.f, factor_units(u, p0, d0) * n);
+  PA_FACTOR_OUTPUTS_CW(PA_X)
 #undef PA_X
   a1.nvalid = off(ta.nvalid, (long)t);
   // the real timestamps (read only by the TM instantiations, factors_dev.h)

@@ -71,7 +71,8 @@ __global__ __launch_bounds__(64) void proj_kernel(int n, const double* __restric
 // 2 = projection / constant-velocity workgroups only
 // RB: the projection factors carry a robust noise model (a.robust_proj; chosen on the host)
 // TM: the launch carries real timestamps (a.dt_pair / a.kp_mask; chosen on the host, factors_dev.h)
-template <bool RB, bool TM>
+// CW: the launch carries the constant-velocity factor on the angular velocity (a.r_cw; the same)
+template <bool RB, bool TM, bool CW>
 __global__ __launch_bounds__(128, 2) void traj_all_kernel(pa_traj_args a, int mode, unsigned long long* ts) {
   __shared__ __attribute__((aligned(16))) double st[trj::STAGE];
   const long wd = ((long)a.T * (a.L - 1) + 63) / 64;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(128, 2) void traj_all_kernel(pa_traj_args a, int mo
     return;
   } else {
     const int wv = threadIdx.x >> 6;
-    traj_unit_wave<RB, TM>(a, 2 * ((long)blockIdx.x - wd) + wv, st + wv * trj::UNIT, ts);
+    traj_unit_wave<RB, TM, CW>(a, 2 * ((long)blockIdx.x - wd) + wv, st + wv * trj::UNIT, ts);
   }
 }
 
@@ -111,6 +112,12 @@ __global__ __launch_bounds__(64) void window_retract_kernel(int T, int L, const 
                                                             double* angvel, double* vel, double* newest) {
   const long f = (long)blockIdx.x * 64 + threadIdx.x;
   if (f < (long)T * L) window_retract_one(f, L, delta, info, pose, angvel, vel, newest);
+}
+
+template <bool CW>
+static auto traj_all_pick(bool rb, bool tm) {
+  return tm ? (rb ? traj_all_kernel<true, true, CW> : traj_all_kernel<false, true, CW>)
+            : (rb ? traj_all_kernel<true, false, CW> : traj_all_kernel<false, false, CW>);
 }
 
 }  // namespace pa
@@ -203,8 +210,11 @@ int pa_debug_trajectory_linearize(const pa_traj_args* a, int mode, unsigned long
   PA_CHECK(!a->kp_mask || a->n_kp <= 32, "trajectory linearize: kp_mask holds one bit per keypoint, n_kp %d > 32",
            a->n_kp);
   const bool rb = a->robust_proj != PA_ROBUST_NONE, tm = a->dt_pair || a->kp_mask;
-  const auto kernel = tm ? (rb ? pa::traj_all_kernel<true, true> : pa::traj_all_kernel<false, true>)
-                         : (rb ? pa::traj_all_kernel<true, false> : pa::traj_all_kernel<false, false>);
+  // (after every older check) the factor on the angular velocity: r_cw is its switch, and with
+  // L == 1 there is no pair to write
+  const bool cw = a->r_cw != nullptr && a->L > 1;
+  PA_CHECK(a->r_cw || !a->err_cw, "trajectory linearize: err_cw is given without r_cw (r_cw switches the factor on)");
+  const auto kernel = cw ? pa::traj_all_pick<true>(rb, tm) : pa::traj_all_pick<false>(rb, tm);
   hipLaunchKernelGGL(kernel, dim3((unsigned)((nd + 63) / 64 + (units + 1) / 2)), dim3(128), 0, (hipStream_t)stream, *a,
                      mode, trace);
   PA_LAUNCH_CHECK();

@@ -799,8 +799,10 @@ namespace trj {
 constexpr int PPW = 4;  // projection factors per lane
 }
 // (RB: a.robust_proj names a robust model, proj_eval<true>; TM: a.kp_mask switches single
-// projection factors off as a.nvalid does whole frames)
-template <bool RB, bool TM = false>
+// projection factors off as a.nvalid does whole frames; CW: a.r_cw is given, the constant-velocity
+// unit also evaluates the factor on the angular velocities -- CW = false never looks at the cw
+// fields and is the code it was before they existed)
+template <bool RB, bool TM = false, bool CW = false>
 __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, double* st, unsigned long long* ts) {
   using trj::PPW;
   const int lane = threadIdx.x & 63;
@@ -892,6 +894,16 @@ __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, do
   if (a.j_cv0) wave_flush<9>(a.j_cv0 + c0 * 9, st + 64 * 3, n);
   if (a.j_cv1) wave_flush<9>(a.j_cv1 + c0 * 9, st + 64 * 12, n);
   if (a.err_cv) wave_flush<1>(a.err_cv + c0, st + 64 * 21, n);
+  if constexpr (CW) {
+    // the same factor on the angular velocities of the pair: r and err only, its Jacobians are
+    // the constants -+ diag(isig_cw) (gn_build_frame folds them in closed form)
+    wave_sync();  // the flushes' LDS reads are done
+    cv_one(a.angvel + f * 3, a.angvel + (f + 1) * 3, a.isig_cw, st + lane * 3, nullptr, nullptr,
+           a.err_cw ? st + 64 * 3 + lane : nullptr);
+    wave_sync();
+    wave_flush<3>(a.r_cw + c0 * 3, st, n);
+    if (a.err_cw) wave_flush<1>(a.err_cw + c0, st + 64 * 3, n);
+  }
   traj_stamp(ts, 4);
   if (ts) {
     __builtin_amdgcn_s_waitcnt(0);
@@ -907,14 +919,14 @@ __device__ __forceinline__ void traj_unit_wave(const pa_traj_args& a, long u, do
 constexpr int TICK_LIN_W = 6;
 constexpr int LIN_STAGE = trj::STAGE + 4 * trj::UNIT;
 static_assert(LIN_STAGE * 8 <= 96 * 1024, "factor staging");
-template <bool RB, bool TM = false>
+template <bool RB, bool TM = false, bool CW = false>
 __device__ __forceinline__ void traj_lin_block(const pa_traj_args& a1, double* st) {
   const int wv = threadIdx.x >> 6;
   const int wp = (a1.L * a1.n_kp + 64 * trj::PPW - 1) / (64 * trj::PPW);  // projection units (<= 2); unit wp: constant velocity
   if (wv < 2) {
     traj_dyn_block<TM>(a1, 0, st, nullptr);  // (its one LDS barrier is matched by every other wave's below)
   } else {
-    if (wv - 2 <= wp) traj_unit_wave<RB, TM>(a1, wv - 2, st + trj::STAGE + (wv - 2) * trj::UNIT, nullptr);
+    if (wv - 2 <= wp) traj_unit_wave<RB, TM, CW>(a1, wv - 2, st + trj::STAGE + (wv - 2) * trj::UNIT, nullptr);
     lds_barrier();
   }
 }

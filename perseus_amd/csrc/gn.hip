@@ -597,13 +597,14 @@ size_t pa_trajectory_gn_workspace(int T, int L) {
   return (T > 0 && L > 0) ? (size_t)T * L * pa::GN_WSF * sizeof(double) : 0;
 }
 
-// pa_trajectory_gn_step with the marginalization prior on frame 0 (prior_info / prior_grad null: none, the parent)
-int pa_trajectory_gn_step_prior(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
-                        const int32_t* status_proj, const double* r_dyn, const double* j_dyn0, const double* j_dyn1,
-                        const double* j_dyn2, const double* j_dyn3, const double* r_cv, const double* j_cv0,
-                        const double* j_cv1, double lambda, double* D, double* E, double* g, double* delta,
-                        int32_t* info, void* ws, size_t ws_bytes, const double* prior_info, const double* prior_grad,
-                        void* stream) {
+// pa_trajectory_gn_step with the marginalization prior on frame 0 (prior_info / prior_grad null: none)
+// and the constant-velocity factor on the angular velocity (r_cw null: none); both null: the parent
+int pa_trajectory_gn_step_cw(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                             const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                             const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
+                             const double* j_cv0, const double* j_cv1, const double* r_cw, const double* isig_cw,
+                             double lambda, double* D, double* E, double* g, double* delta, int32_t* info, void* ws,
+                             size_t ws_bytes, const double* prior_info, const double* prior_grad, void* stream) {
   PA_CHECK(T >= 0 && L >= 1 && n_kp >= 0 && n_kp <= pa::GN_KMAX, "gn: T %d L %d n_kp %d (<= %d)", T, L, n_kp,
            pa::GN_KMAX);
   if (T == 0) return PA_OK;
@@ -618,11 +619,23 @@ int pa_trajectory_gn_step_prior(int T, int L, int n_kp, const double* r_proj, co
            pa_trajectory_gn_workspace(T, L));
   const pa::GnArgs a{T,     L,      n_kp,   r_proj, j_proj, status_proj, r_dyn, j_dyn0, j_dyn1, j_dyn2, j_dyn3,
                      r_cv,  j_cv0,  j_cv1,  lambda, D,      E,           g,     delta,  info,   (double*)ws,
-                     pa::g_gn_trace, prior_info, prior_grad};
+                     pa::g_gn_trace, prior_info, prior_grad, r_cw, isig_cw};
+  PA_CHECK(!r_cw || isig_cw, "gn: r_cw is given without isig_cw (the factor's Jacobians are -+ diag(isig_cw))");
   const hipStream_t s = (hipStream_t)stream;
   pa::gn_for_kp(n_kp, [&](auto rp) { pa::launch_gn<decltype(rp)::value>(a, pa::g_gn_na, s); });
   PA_LAUNCH_CHECK();
   return PA_OK;
+}
+
+int pa_trajectory_gn_step_prior(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                                const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                                const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
+                                const double* j_cv0, const double* j_cv1, double lambda, double* D, double* E,
+                                double* g, double* delta, int32_t* info, void* ws, size_t ws_bytes,
+                                const double* prior_info, const double* prior_grad, void* stream) {
+  return pa_trajectory_gn_step_cw(T, L, n_kp, r_proj, j_proj, status_proj, r_dyn, j_dyn0, j_dyn1, j_dyn2, j_dyn3, r_cv,
+                                  j_cv0, j_cv1, nullptr, nullptr, lambda, D, E, g, delta, info, ws, ws_bytes,
+                                  prior_info, prior_grad, stream);
 }
 
 int pa_trajectory_gn_step(int T, int L, int n_kp, const double* r_proj, const double* j_proj,

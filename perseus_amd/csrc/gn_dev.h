@@ -28,18 +28,24 @@ struct GnArgs {
   // the marginalization prior on frame 0 (prior.hip): Lambda (T, 12, 12) and its gradient
   // Lambda xi - eta (T, 12), added to D_0 / g_0 by gn_build_frame; null = no prior
   const double *p_info, *p_grad;
+  // the constant-velocity factor on the angular velocity (pa_traj_args.r_cw): its whitened
+  // residuals (T*(L-1), 3) and its whitening (3), folded into the blocks in closed form by
+  // gn_build_frame; r_cw null = off
+  const double *r_cw, *isig_cw;
 };
 
-// the step on the factor set s (delta only: no D / E / g outputs, no trace)
+// the step on the factor set s (delta only: no D / E / g outputs, no trace); isig_cw: the
+// whitening that goes with s.r_cw (not looked at when that is null)
 __host__ __device__ __forceinline__ GnArgs gn_args(int T, int L, int K, const FactorSet& s, double lambda,
-                                                   double* delta, int32_t* info, double* ws) {
+                                                   double* delta, int32_t* info, double* ws,
+                                                   const double* isig_cw = nullptr) {
   return GnArgs{T,      L,        K,        s.r_proj, s.j_proj, s.status, s.r_dyn, s.j_dyn0, s.j_dyn1, s.j_dyn2, s.j_dyn3,
                 s.r_cv, s.j_cv0,  s.j_cv1,  lambda,   nullptr,  nullptr,  nullptr, delta,    info,     ws,       nullptr,
-                nullptr, nullptr};
+                nullptr, nullptr, s.r_cw,   isig_cw};
 }
 // ... on the factor outputs ta names
 inline GnArgs gn_args(const pa_traj_args& ta, double lambda, double* delta, int32_t* info, double* ws) {
-  return gn_args(ta.T, ta.L, ta.n_kp, factor_set(ta), lambda, delta, info, ws);
+  return gn_args(ta.T, ta.L, ta.n_kp, factor_set(ta), lambda, delta, info, ws, ta.isig_cw);
 }
 
 // assembler waves per trajectory and solver (pa_debug_gn_set_assemblers: na + 8 * legacy;
@@ -341,6 +347,33 @@ __device__ __forceinline__ void gn_build_frame(const GnArgs& a, long f, const Gn
         const double an = li < NV ? ANT[li][row] : 0.0;
         const double bt = li < NV ? BT[li][row] : 0.0;
         cE = __builtin_amdgcn_mfma_f64_16x16x4f64(an, bt, cE, 0, 0, 0);
+      }
+    }
+  }
+  // the constant-velocity factor on the angular velocity, pairs (l-1, l) and (l, l+1): its rows
+  // are -s_i on x_l's variable 6 + i and +s_i on x_{l+1}'s (s = isig_cw), so with r the whitened
+  // residuals  D_l[6+i][6+i] += s_i^2 per pair,  E_l[6+i][6+i] -= s_i^2,
+  // g_l[6+i] += s_i (r_{l-1,i} - r_{l,i})  -- no staged rows.  Rows 6, 7, 8 of the C layout are
+  // (lk, v) = (2, 1), (3, 1), (0, 2); one lane each holds the diagonal entry (li == row) and the
+  // g entry (li == NV).  (The branch is uniform; with the factor off nothing here changes cD / cE.)
+  if (a.r_cw != nullptr && npair > 0) {
+    const int i = lk >= 2 ? lk - 2 : 2, row = 6 + i;
+    const bool hd = lk != 1 && li == row, hg = lk != 1 && li == NV;
+    if (hd || hg) {
+      const double s = a.isig_cw[i];
+      const long un = (long)t * npair + (nxt ? l : 0), up = (long)t * npair + (prv ? l - 1 : 0);
+      const double rn = nxt ? a.r_cw[un * 3 + i] : 0.0, rq = prv ? a.r_cw[up * 3 + i] : 0.0;
+      const double s2 = s * s;
+      const double addD = hd ? (nxt ? s2 : 0.0) + (prv ? s2 : 0.0) : s * (rq - rn);
+      if (lk >= 2)
+        cD[1] += addD;
+      else
+        cD[2] += addD;
+      if (hd && nxt) {
+        if (lk >= 2)
+          cE[1] -= s2;
+        else
+          cE[2] -= s2;
       }
     }
   }

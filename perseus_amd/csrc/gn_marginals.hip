@@ -209,13 +209,14 @@ size_t pa_trajectory_marginals_workspace(int T, int L) {
   return (T > 0 && L > 0) ? (size_t)T * L * pa::MG_WSF * sizeof(double) : 0;
 }
 
-// pa_trajectory_marginals with the marginalization prior on frame 0 (prior_info / prior_grad null: none, the parent)
-int pa_trajectory_marginals_prior(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
-                          const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
-                          const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
-                          const double* j_cv0, const double* j_cv1, double lambda, double* cov, double* cross,
-                          double* cov_newest, int32_t* info, void* ws, size_t ws_bytes, const double* prior_info,
-                          const double* prior_grad, void* stream) {
+// pa_trajectory_marginals with the marginalization prior on frame 0 (prior_info / prior_grad null: none)
+// and the constant-velocity factor on the angular velocity (r_cw null: none); both null: the parent
+int pa_trajectory_marginals_cw(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                               const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                               const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
+                               const double* j_cv0, const double* j_cv1, const double* r_cw, const double* isig_cw,
+                               double lambda, double* cov, double* cross, double* cov_newest, int32_t* info, void* ws,
+                               size_t ws_bytes, const double* prior_info, const double* prior_grad, void* stream) {
   PA_CHECK(T >= 0 && L >= 2 && n_kp >= 0 && n_kp <= pa::GN_KMAX, "marginals: T %d L %d (>= 2) n_kp %d (<= %d)", T, L,
            n_kp, pa::GN_KMAX);
   if (T == 0) return PA_OK;
@@ -231,7 +232,9 @@ int pa_trajectory_marginals_prior(int T, int L, int n_kp, const double* r_proj, 
            pa_trajectory_marginals_workspace(T, L));
   const pa::GnArgs a{T,     L,     n_kp,  r_proj, j_proj,  status_proj, r_dyn,   j_dyn0,  j_dyn1, j_dyn2,      j_dyn3,
                      r_cv,  j_cv0, j_cv1, lambda, nullptr, nullptr,     nullptr, nullptr, info,   (double*)ws, nullptr,
-                     prior_info, prior_grad};
+                     prior_info, prior_grad, r_cw, isig_cw};
+  PA_CHECK(!r_cw || isig_cw,
+           "marginals: r_cw is given without isig_cw (the factor's Jacobians are -+ diag(isig_cw))");
   const hipStream_t s = (hipStream_t)stream;
   pa::gn_for_kp(n_kp, [&](auto rp) {
     hipLaunchKernelGGL(pa::gn_marginals_kernel<decltype(rp)::value>, dim3(T), dim3(128), 0, s, a, cov, cross,
@@ -239,6 +242,18 @@ int pa_trajectory_marginals_prior(int T, int L, int n_kp, const double* r_proj, 
   });
   PA_LAUNCH_CHECK();
   return PA_OK;
+}
+
+int pa_trajectory_marginals_prior(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                                  const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                                  const double* j_dyn1, const double* j_dyn2, const double* j_dyn3,
+                                  const double* r_cv, const double* j_cv0, const double* j_cv1, double lambda,
+                                  double* cov, double* cross, double* cov_newest, int32_t* info, void* ws,
+                                  size_t ws_bytes, const double* prior_info, const double* prior_grad,
+                                  void* stream) {
+  return pa_trajectory_marginals_cw(T, L, n_kp, r_proj, j_proj, status_proj, r_dyn, j_dyn0, j_dyn1, j_dyn2, j_dyn3,
+                                    r_cv, j_cv0, j_cv1, nullptr, nullptr, lambda, cov, cross, cov_newest, info, ws,
+                                    ws_bytes, prior_info, prior_grad, stream);
 }
 
 int pa_trajectory_marginals(int T, int L, int n_kp, const double* r_proj, const double* j_proj,

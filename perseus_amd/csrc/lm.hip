@@ -43,7 +43,7 @@ struct LmPriorDev {
   double *err, *err_out;                    // (T) e_prior at the current state (workspace), the caller's or nullptr
 };
 struct LmDev {
-  FactorSet s0, s1;              // the caller's factor outputs, the workspace's
+  FactorSetReq s0, s1;           // the caller's factor outputs, the workspace's (the required ones; cw0 / cw1 below)
   double *pose, *vel, *angvel;   // the trial state (T*L, 12 / 3 / 3)
   double* delta;                 // (T*L, 12)
   double *C, *lam;               // (T) the current cost and damping
@@ -54,10 +54,23 @@ struct LmDev {
   pa_lm_params p;
   int pending;  // the newest frame's keypoints are not in yet (pa_window_lm_solve): its projections get status 3
   LmPriorDev pr;
+  // the factor on the angular velocity: its outputs in set 0 / set 1 (r_cw null in both: off) and
+  // its whitening.  Last, so that everything above sits where it did before the factor existed
+  double *r_cw0, *err_cw0, *r_cw1, *err_cw1;
+  const double* isig_cw;
 };
 
-__device__ __forceinline__ FactorSet lm_pick(const LmDev& d, int which) {  // (uniform selects, no indexed copy)
-  return factor_set_select(d.s0, d.s1, which != 0);
+// set `which`: per pointer a select between the two kernel-argument structs (uniform; an indexed
+// copy, sets[which], would put both sets in scratch)
+__device__ __forceinline__ FactorSet lm_pick(const LmDev& d, int which) {
+  const bool w = which != 0;
+  FactorSet s;
+#define PA_X(f, V, n, u) s.f = w ? d.s1.f : d.s0.f;
+  PA_FACTOR_OUTPUTS(PA_X)
+#undef PA_X
+  s.r_cw = w ? d.r_cw1 : d.r_cw0;
+  s.err_cw = w ? d.err_cw1 : d.err_cw0;
+  return s;
 }
 
 // loads of what this workgroup's other waves stored earlier in the launch (after a
@@ -78,8 +91,10 @@ __device__ __forceinline__ void lm_copy(V* dst, const V* src, long n) {
 // iteration k into the set that is not current, then the decision.  RB: ta.robust_proj names a
 // robust noise model (the cost is then the sum of its rho; the decision logic is the same).
 // PR: d.pr holds a prior on frame 0.  TM: ta carries real timestamps (dt_pair / kp_mask,
-// factors_dev.h; traj_view hands the trajectory's slices on)
-template <bool RB, bool PR, bool TM>
+// factors_dev.h; traj_view hands the trajectory's slices on).  CW: ta carries the constant-velocity
+// factor on the angular velocity (r_cw / err_cw): its err entries enter the cost right after
+// err_cv's; CW = false is the code, the index layout and the bits it was
+template <bool RB, bool PR, bool TM, bool CW>
 __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta, LmDev d, int k) {
   __shared__ __attribute__((aligned(16))) double st[LIN_STAGE];
   __shared__ int dec_s;
@@ -100,7 +115,7 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta
     a1.pose = k > 0 ? d.pose + f0 * 12 : xp;  // (the trial state)
     a1.vel = k > 0 ? d.vel + f0 * 3 : xv;
     a1.angvel = k > 0 ? d.angvel + f0 * 3 : xw;
-    traj_lin_block<RB, TM>(a1, st);
+    traj_lin_block<RB, TM, CW>(a1, st);
     if constexpr (PR) {
       // the prior at frame 0 of the state just linearized: grad to the target set, e_prior to wave 0
       __shared__ double pxi[gn::NV], pes[gn::NV], pe_s;
@@ -124,15 +139,18 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta
     double s = 0.0;
     bool bad = false;
     if (!pivot) {
-      const int nd = L - 1, np = L * K, n = 2 * nd + np;
+      constexpr int NPF = CW ? 3 : 2;  // pair factors: dynamics, constant velocity (, angular velocity)
+      const int nd = L - 1, np = L * K, n = NPF * nd + np;
       for (int i = lane; i < n; i += 64) {
         double v;
         if (i < nd) {
           v = lm_ld(so.err_dyn + d0 + i);
         } else if (i < 2 * nd) {
           v = lm_ld(so.err_cv + d0 + i - nd);
+        } else if (CW && i < 3 * nd) {
+          v = lm_ld(so.err_cw + d0 + i - 2 * nd);
         } else {
-          const int j = i - 2 * nd;
+          const int j = i - NPF * nd;
           int32_t sn = lm_ld(so.status + p0 + j);
           if (d.pending && j >= (L - 1) * K) {  // out of the cost, the guard and (status 3) the step's assembly
             sn = 3;
@@ -210,6 +228,10 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void lm_lin_kernel(pa_traj_args ta
   lm_copy(d.s0.f + factor_units(u, p0, d0) * n, d.s1.f + factor_units(u, p0, d0) * n, factor_units(u, np, nd) * n);
     PA_FACTOR_OUTPUTS(PA_X)
 #undef PA_X
+    if constexpr (CW) {
+      lm_copy(d.r_cw0 + d0 * 3, d.r_cw1 + d0 * 3, nd * 3);
+      lm_copy(d.err_cw0 + d0, d.err_cw1 + d0, nd);
+    }
     if constexpr (PR) lm_copy(d.pr.g0 + (size_t)t * gn::NV, d.pr.g1 + (size_t)t * gn::NV, (long)gn::NV);
   }
 }
@@ -229,7 +251,7 @@ __global__ __launch_bounds__(64 * GN_CR_W, 1) void lm_step_kernel(int T, int L, 
   const int t = blockIdx.x;
   if (d.done[t] != 0) return;  // (uniform)
   const int cur = d.cur[t];
-  GnArgs g = gn_args(T, L, K, lm_pick(d, cur), d.lam[t], d.delta, d.info, nullptr);
+  GnArgs g = gn_args(T, L, K, lm_pick(d, cur), d.lam[t], d.delta, d.info, nullptr, d.isig_cw);
   if constexpr (PR) {
     g.p_info = d.pr.info;
     g.p_grad = cur ? d.pr.g1 : d.pr.g0;
@@ -254,7 +276,7 @@ __global__ __launch_bounds__(64 * GN_CR_W, 1) void lm_step_kernel(int T, int L, 
 // set 1's prior gradient (T, 12) and the current e_prior (T); every array 16-B aligned
 struct LmLayout {
 #define PA_X(f, V, n, u) size_t f;
-  PA_FACTOR_OUTPUTS(PA_X)
+  PA_FACTOR_OUTPUTS_ALL(PA_X)
 #undef PA_X
   size_t pose, vel, angvel, delta, C, lam, done, cur, info, hist, pgrad, perr, bytes;
 };
@@ -268,7 +290,7 @@ static LmLayout lm_layout(int T, int L, int K, int max_iters, bool prior) {
   };
   const size_t F = (size_t)T * L, np = F * K, nd = (size_t)T * (L - 1);
 #define PA_X(f, V, n, u) o.f = take(factor_units(u, np, nd) * n, sizeof(V));
-  PA_FACTOR_OUTPUTS(PA_X)
+  PA_FACTOR_OUTPUTS_ALL(PA_X)  // (the optional pair always has its room: the size does not depend on the switch)
 #undef PA_X
   o.pose = take(F * 12, 8);
   o.vel = take(F * 3, 8);
@@ -287,6 +309,14 @@ static LmLayout lm_layout(int T, int L, int K, int max_iters, bool prior) {
   }
   o.bytes = at;
   return o;
+}
+
+template <bool CW>
+static auto lm_lin_pick(bool rb, bool prior, bool tm) {
+  return tm ? (prior ? (rb ? lm_lin_kernel<true, true, true, CW> : lm_lin_kernel<false, true, true, CW>)
+                     : (rb ? lm_lin_kernel<true, false, true, CW> : lm_lin_kernel<false, false, true, CW>))
+            : (prior ? (rb ? lm_lin_kernel<true, true, false, CW> : lm_lin_kernel<false, true, false, CW>)
+                     : (rb ? lm_lin_kernel<true, false, false, CW> : lm_lin_kernel<false, false, false, CW>));
 }
 
 }  // namespace pa
@@ -333,6 +363,9 @@ static int lm_solve_impl(const pa_traj_args* ta, const pa_lm_params* p, int pend
   const pa::LmLayout o = pa::lm_layout(T, L, K, p->max_iters, prior != nullptr);
   PA_CHECK(ws && ws_bytes >= o.bytes, "lm: workspace %zu < %zu", ws ? ws_bytes : (size_t)0, o.bytes);
   PA_CHECK(((uintptr_t)ws & 15) == 0, "lm: workspace not 16-byte aligned");
+  // the factor on the angular velocity (r_cw switches it on; off, neither of the two is looked at)
+  PA_CHECK(!ta->r_cw || ta->isig_cw, "lm: r_cw is given without isig_cw (the cost is defined on whitened residuals)");
+  PA_CHECK(!ta->r_cw || ta->err_cw, "lm: r_cw is given without err_cw (the cost sums the factor's err)");
   char* w = (char*)ws;
   auto f64 = [&](size_t off) { return (double*)(w + off); };
   auto i32 = [&](size_t off) { return (int32_t*)(w + off); };
@@ -341,6 +374,12 @@ static int lm_solve_impl(const pa_traj_args* ta, const pa_lm_params* p, int pend
 #define PA_X(f, V, n, u) d.s1.f = (V*)(w + o.f);
   PA_FACTOR_OUTPUTS(PA_X)
 #undef PA_X
+  const bool cw = ta->r_cw != nullptr;
+  d.r_cw0 = ta->r_cw;
+  d.err_cw0 = cw ? ta->err_cw : nullptr;
+  d.r_cw1 = cw ? f64(o.r_cw) : nullptr;  // (off in both sets)
+  d.err_cw1 = cw ? f64(o.err_cw) : nullptr;
+  d.isig_cw = ta->isig_cw;
   d.pose = f64(o.pose);
   d.vel = f64(o.vel);
   d.angvel = f64(o.angvel);
@@ -365,11 +404,7 @@ static int lm_solve_impl(const pa_traj_args* ta, const pa_lm_params* p, int pend
   const hipStream_t s = (hipStream_t)stream;
   const bool rb = ta->robust_proj != PA_ROBUST_NONE;
   const bool tm = ta->dt_pair || ta->kp_mask;
-  const auto lin_kernel =
-      tm ? (prior ? (rb ? pa::lm_lin_kernel<true, true, true> : pa::lm_lin_kernel<false, true, true>)
-                  : (rb ? pa::lm_lin_kernel<true, false, true> : pa::lm_lin_kernel<false, false, true>))
-         : (prior ? (rb ? pa::lm_lin_kernel<true, true, false> : pa::lm_lin_kernel<false, true, false>)
-                  : (rb ? pa::lm_lin_kernel<true, false, false> : pa::lm_lin_kernel<false, false, false>));
+  const auto lin_kernel = cw ? pa::lm_lin_pick<true>(rb, prior != nullptr, tm) : pa::lm_lin_pick<false>(rb, prior != nullptr, tm);
   for (int k = 0; k <= p->max_iters; ++k) {
     if (k > 0)
       pa::gn_for_kp(K, [&](auto rp) {

@@ -27,7 +27,9 @@ namespace pa {
 // TM (here and in pose_tick_post_kernel): ta carries real timestamps (dt_pair / kp_mask; the host
 // picks the instantiation, factors_dev.h): the advance moves both rings and lands dt_new /
 // mask_new, the factors read them after the barrier that follows it.
-template <bool RB, bool TM>
+// CW: ta carries the constant-velocity factor on the angular velocity (r_cw; the host picks the
+// instantiation, factors_dev.h).  It needs no keypoints, so the pre half (y_new null) has all of it.
+template <bool RB, bool TM, bool CW>
 __global__ __launch_bounds__(64 * TICK_LIN_W) void pose_tick_lin_kernel(pa_traj_args ta, const float* __restrict__ y_new) {
   __shared__ __attribute__((aligned(16))) double st[LIN_STAGE];
   const int t = blockIdx.x, L = ta.L, K = ta.n_kp;
@@ -43,7 +45,7 @@ __global__ __launch_bounds__(64 * TICK_LIN_W) void pose_tick_lin_kernel(pa_traj_
                         ta.vel_frame, const_cast<int32_t*>(ta.nvalid));
   __syncthreads();
   const pa_traj_args a1 = traj_view(ta, t, factor_set(ta));
-  traj_lin_block<RB, TM>(a1, st);
+  traj_lin_block<RB, TM, CW>(a1, st);
   if (!y_new) {  // (uniform)
     __syncthreads();  // the unit waves' status stores come first
     if ((int)threadIdx.x < K) a1.status[(long)(L - 1) * K + threadIdx.x] = 3;
@@ -211,6 +213,12 @@ __global__ __launch_bounds__(64 * GN_CR_W, 1) void pose_tick_post_kernel(pa_traj
                          const_cast<double*>(ta.angvel), const_cast<double*>(ta.vel), newest);
 }
 
+template <bool CW>
+static auto pose_tick_lin_pick(bool rb, bool tm) {
+  return tm ? (rb ? pose_tick_lin_kernel<true, true, CW> : pose_tick_lin_kernel<false, true, CW>)
+            : (rb ? pose_tick_lin_kernel<true, false, CW> : pose_tick_lin_kernel<false, false, CW>);
+}
+
 }  // namespace pa
 
 extern "C" {
@@ -249,6 +257,14 @@ static int pose_tick_check(const pa_traj_args* ta, double lambda, const char* wh
   return PA_OK;
 }
 
+// the factor on the angular velocity (r_cw switches it on): the step needs its whitening.  Every
+// entry point runs this after all of its older checks
+static int pose_tick_cw_check(const pa_traj_args* ta, const char* who) {
+  PA_CHECK(!ta->r_cw || ta->isig_cw, "%s: r_cw is given without isig_cw (the step needs the factor whitened)", who);
+  PA_CHECK(ta->r_cw || !ta->err_cw, "%s: err_cw is given without r_cw (r_cw switches the factor on)", who);
+  return PA_OK;
+}
+
 static int pose_tick_ws_check(const pa_traj_args* ta, const void* ws, size_t ws_bytes, const char* who) {
   const size_t need = pa_window_pose_tick_workspace(ta->T, ta->L);
   PA_CHECK(ws && ws_bytes >= need, "%s: workspace %zu < %zu", who, ws_bytes, need);
@@ -258,8 +274,7 @@ static int pose_tick_ws_check(const pa_traj_args* ta, const void* ws, size_t ws_
 // advance + linearize (y_new null: the split tick's pre half), with or without a robust noise model
 static void launch_lin(const pa_traj_args* ta, const float* y_new, hipStream_t s) {
   const bool rb = ta->robust_proj != PA_ROBUST_NONE, tm = ta->dt_pair || ta->kp_mask;
-  const auto kernel = tm ? (rb ? pa::pose_tick_lin_kernel<true, true> : pa::pose_tick_lin_kernel<false, true>)
-                         : (rb ? pa::pose_tick_lin_kernel<true, false> : pa::pose_tick_lin_kernel<false, false>);
+  const auto kernel = ta->r_cw ? pa::pose_tick_lin_pick<true>(rb, tm) : pa::pose_tick_lin_pick<false>(rb, tm);
   hipLaunchKernelGGL(kernel, dim3(ta->T), dim3(64 * pa::TICK_LIN_W), 0, s, *ta, y_new);
 }
 
@@ -286,6 +301,7 @@ int pa_window_pose_tick_prior(const pa_traj_args* ta, const float* y_new, double
   int rc = pose_tick_check(ta, lambda, "pose tick", true);
   if (rc != PA_OK || ta->T == 0) return rc;
   if ((rc = prior_pair_check(prior_info, prior_grad, "pose tick")) != PA_OK) return rc;
+  if ((rc = pose_tick_cw_check(ta, "pose tick")) != PA_OK) return rc;
   const int T = ta->T;
   pa::GnArgs g = pa::gn_args(*ta, lambda, delta, info, nullptr);
   g.p_info = prior_info;
@@ -315,6 +331,7 @@ int pa_window_pose_tick_pre_prior(const pa_traj_args* ta, double lambda, void* w
   if (rc != PA_OK || ta->T == 0) return rc;
   if ((rc = prior_pair_check(prior_info, prior_grad, "pose tick pre")) != PA_OK) return rc;
   if ((rc = pose_tick_ws_check(ta, ws, ws_bytes, "pose tick pre")) != PA_OK) return rc;
+  if ((rc = pose_tick_cw_check(ta, "pose tick pre")) != PA_OK) return rc;
   const hipStream_t s = (hipStream_t)stream;
   launch_lin(ta, nullptr, s);
   launch_pre(ta, lambda, ws, prior_info, prior_grad, s);
@@ -332,6 +349,7 @@ int pa_window_pose_tick_reduce_prior(const pa_traj_args* ta, double lambda, void
   if (rc != PA_OK || ta->T == 0) return rc;
   if ((rc = prior_pair_check(prior_info, prior_grad, "pose tick reduce")) != PA_OK) return rc;
   if ((rc = pose_tick_ws_check(ta, ws, ws_bytes, "pose tick reduce")) != PA_OK) return rc;
+  if ((rc = pose_tick_cw_check(ta, "pose tick reduce")) != PA_OK) return rc;
   launch_pre(ta, lambda, ws, prior_info, prior_grad, (hipStream_t)stream);
   PA_LAUNCH_CHECK();
   return PA_OK;
@@ -347,6 +365,7 @@ int pa_window_pose_tick_post(const pa_traj_args* ta, const float* y_new, const v
   if (rc != PA_OK || ta->T == 0) return rc;
   PA_CHECK(y_new && delta && info, "pose tick post: null y_new / delta / info");
   if ((rc = pose_tick_ws_check(ta, ws, ws_bytes, "pose tick post")) != PA_OK) return rc;
+  if ((rc = pose_tick_cw_check(ta, "pose tick post")) != PA_OK) return rc;
   const bool rb = ta->robust_proj != PA_ROBUST_NONE, tm = ta->kp_mask != nullptr;
   const auto kernel = tm ? (rb ? pa::pose_tick_post_kernel<true, true> : pa::pose_tick_post_kernel<false, true>)
                          : (rb ? pa::pose_tick_post_kernel<true, false> : pa::pose_tick_post_kernel<false, false>);

@@ -108,6 +108,16 @@ __global__ __launch_bounds__(64) void marginalize_kernel(GnArgs a, MargArgs m) {
       for (int v = 0; v < 3; ++v)  // rows lk + 4v < 12
         if (li <= NV) Fx[(lk + 4 * v) * 13 + li] = cF[v];
       wave_order();
+      // the pair (0, 1)'s factor on the angular velocity (gn_build_frame's closed form): its x_1
+      // part is +s_i on variable 6 + i, so F[6+i][6+i] += s_i^2 and h[6+i] += s_i r_{0,i}
+      if (a.r_cw != nullptr) {  // (uniform)
+        if (i < 3) {
+          const double s = a.isig_cw[i];
+          Fx[(6 + i) * 13 + 6 + i] += s * s;
+          Fx[(6 + i) * 13 + NV] += s * a.r_cw[(size_t)t * (L - 1) * 3 + i];
+        }
+        wave_order();
+      }
 #pragma unroll
       for (int c = 0; c < 4; ++c) sv[c] = Fx[r * 13 + c0 + c];
       b = Fx[r * 13 + NV];
@@ -167,14 +177,16 @@ int pa_window_prior_linearize(int T, int L, int frame, const double* info, const
   return PA_OK;
 }
 
-int pa_window_marginalize(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
-                          const int32_t* status_proj, const double* r_dyn, const double* j_dyn0, const double* j_dyn1,
-                          const double* j_dyn2, const double* j_dyn3, const double* r_cv, const double* j_cv0,
-                          const double* j_cv1, const double* prior_info_in, const double* prior_grad_in, double lambda,
-                          const double* delta, const int32_t* gn_info, const int32_t* nvalid, const double* pose,
-                          const double* angvel, const double* vel, double* info_out, double* eta_out,
-                          double* xbar_pose_out, double* xbar_angvel_out, double* xbar_vel_out, int32_t* minfo,
-                          void* stream) {
+// pa_window_marginalize with the constant-velocity factor on the angular velocity (r_cw null: the parent)
+int pa_window_marginalize_cw(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                             const int32_t* status_proj, const double* r_dyn, const double* j_dyn0,
+                             const double* j_dyn1, const double* j_dyn2, const double* j_dyn3, const double* r_cv,
+                             const double* j_cv0, const double* j_cv1, const double* prior_info_in,
+                             const double* prior_grad_in, const double* r_cw, const double* isig_cw, double lambda,
+                             const double* delta, const int32_t* gn_info, const int32_t* nvalid, const double* pose,
+                             const double* angvel, const double* vel, double* info_out, double* eta_out,
+                             double* xbar_pose_out, double* xbar_angvel_out, double* xbar_vel_out, int32_t* minfo,
+                             void* stream) {
   PA_CHECK(T >= 0 && L >= 2 && n_kp >= 0 && n_kp <= pa::GN_KMAX, "marginalize: T %d L %d (>= 2) n_kp %d (<= %d)", T, L,
            n_kp, pa::GN_KMAX);
   PA_CHECK(lambda >= 0.0, "marginalize: lambda %g < 0", lambda);
@@ -189,7 +201,9 @@ int pa_window_marginalize(int T, int L, int n_kp, const double* r_proj, const do
            "marginalize: null output pointer");
   const pa::GnArgs a{T,     L,     n_kp,  r_proj, j_proj,  status_proj, r_dyn,   j_dyn0,  j_dyn1,  j_dyn2,  j_dyn3,
                      r_cv,  j_cv0, j_cv1, lambda, nullptr, nullptr,     nullptr, nullptr, nullptr, nullptr, nullptr,
-                     prior_info_in, prior_grad_in};
+                     prior_info_in, prior_grad_in, r_cw, isig_cw};
+  PA_CHECK(!r_cw || isig_cw,
+           "marginalize: r_cw is given without isig_cw (the factor's Jacobians are -+ diag(isig_cw))");
   const pa::MargArgs m{delta, gn_info, nvalid, pose, angvel, vel, info_out, eta_out, xbar_pose_out, xbar_angvel_out,
                        xbar_vel_out, minfo};
   pa::gn_for_kp(n_kp, [&](auto rp) {
@@ -197,6 +211,20 @@ int pa_window_marginalize(int T, int L, int n_kp, const double* r_proj, const do
   });
   PA_LAUNCH_CHECK();
   return PA_OK;
+}
+
+int pa_window_marginalize(int T, int L, int n_kp, const double* r_proj, const double* j_proj,
+                          const int32_t* status_proj, const double* r_dyn, const double* j_dyn0, const double* j_dyn1,
+                          const double* j_dyn2, const double* j_dyn3, const double* r_cv, const double* j_cv0,
+                          const double* j_cv1, const double* prior_info_in, const double* prior_grad_in, double lambda,
+                          const double* delta, const int32_t* gn_info, const int32_t* nvalid, const double* pose,
+                          const double* angvel, const double* vel, double* info_out, double* eta_out,
+                          double* xbar_pose_out, double* xbar_angvel_out, double* xbar_vel_out, int32_t* minfo,
+                          void* stream) {
+  return pa_window_marginalize_cw(T, L, n_kp, r_proj, j_proj, status_proj, r_dyn, j_dyn0, j_dyn1, j_dyn2, j_dyn3, r_cv,
+                                  j_cv0, j_cv1, prior_info_in, prior_grad_in, nullptr, nullptr, lambda, delta, gn_info,
+                                  nvalid, pose, angvel, vel, info_out, eta_out, xbar_pose_out, xbar_angvel_out,
+                                  xbar_vel_out, minfo, stream);
 }
 
 }  // extern "C"

@@ -62,7 +62,8 @@ def _isig(sigmas, dim, dev):
 def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: int, dt: float,
                          vel_frame: str = "world", camera_pose=None, H: int = 256, W: int = 256,
                          proj_sigmas=None, dyn_sigmas=None, cv_sigmas=None, jacobians: bool = True,
-                         nvalid: torch.Tensor | None = None, proj_robust=None, dt_pair=None, kp_mask=None):
+                         nvalid: torch.Tensor | None = None, proj_robust=None, dt_pair=None, kp_mask=None,
+                         cw_sigmas=None):
     """Stage inputs on the device and allocate outputs: returns (args, out).  `args`
     (a pa_traj_args) can be launched repeatedly with `launch(args, device)`; `out`
     holds the output tensors (Jacobians as (n, cols, rows) column-major buffers) and
@@ -78,7 +79,11 @@ def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T
     bit k set = keypoint k of that frame was measured; the projection factors of cleared bits get
     status 2 and zero residual / Jacobian, as nvalid's (pa_traj_args.kp_mask; K <= 32).  Arrays
     are staged; a device tensor of the right type (f64 / int32, contiguous) is used in place and
-    read at every launch.  Both are in out["dt_pair"] / out["kp_mask"] and kept alive."""
+    read at every launch.  Both are in out["dt_pair"] / out["kp_mask"] and kept alive.
+    cw_sigmas (optional, 3 or one value, rad/s): switches on the ConstantVelocityFactor on the
+    ANGULAR velocity of every frame pair (pa_traj_args.r_cw): out["r_cw"] (T*(L-1), 3) and
+    out["err_cw"] (T*(L-1),), whitened, and out["isig_cw"]; GNPlan, MarginalsPlan, PriorPlan.marginalize,
+    LMPlan and the streaming ticks honour the factor when `out` / `args` carry it.  None: off."""
     if y.device.type != "cuda":
         raise RuntimeError("linearize_trajectories expects the detector output on the GPU (no CPU fallback)")
     if vel_frame not in ("world", "body"):
@@ -96,6 +101,7 @@ def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T
     Kt = _f64(K, dev, (5,))
     Tc = _f64(camera_pose, dev, (12,))
     isp, isd, isc = _isig(proj_sigmas, 2, dev), _isig(dyn_sigmas, 6, dev), _isig(cv_sigmas, 3, dev)
+    isw = _isig(cw_sigmas, 3, dev)
     n, m = F * nk, T * max(L - 1, 0)
 
     def e(*shape, dtype=torch.float64):
@@ -114,6 +120,9 @@ def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T
     a.dt = float(dt)
     a.vel_frame = _lib.VEL_WORLD if vel_frame == "world" else _lib.VEL_BODY
     a.isig_proj, a.isig_dyn, a.isig_cv = _lib.ptr(isp), _lib.ptr(isd), _lib.ptr(isc)
+    if isw is not None:  # the factor on the angular velocity: r_cw is its switch
+        out["r_cw"], out["err_cw"], out["isig_cw"] = e(m, 3), e(m), isw
+        a.isig_cw, a.r_cw, a.err_cw = isw.data_ptr(), out["r_cw"].data_ptr(), out["err_cw"].data_ptr()
     if nvalid is not None and (nvalid.device != dev or nvalid.dtype != torch.int32 or nvalid.numel() != T
                                or not nvalid.is_contiguous()):
         raise RuntimeError(f"nvalid must be a contiguous int32 ({T},) tensor on {dev}")
@@ -127,7 +136,7 @@ def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T
     out["dt_pair"], out["kp_mask"] = dtp, msk
     for k in ("r_proj", "err_proj", "status", "r_dyn", "err_dyn", "r_cv", "err_cv", *_JAC):
         setattr(a, k, _lib.ptr(out[k]))
-    out["_keep"] = (y, P, V, Wv, Cn, Kt, Tc, isp, isd, isc, nvalid, dtp, msk)  # inputs stay alive until the stream drains
+    out["_keep"] = (y, P, V, Wv, Cn, Kt, Tc, isp, isd, isc, nvalid, dtp, msk, isw)  # inputs stay alive until the stream drains
     return a, out
 
 
@@ -200,11 +209,18 @@ class GNPlan:
         """One pa_trajectory_gn_step on the device's current stream."""
         lin, out, p = self.lin, self.out, _lib.ptr
         with torch.cuda.device(self.dev):
-            args = (self.T, self.L, self.n_kp, p(lin["r_proj"]), p(lin["j_proj"]), p(lin.get("status")),
-                    p(lin["r_dyn"]), p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]),
-                    p(lin["r_cv"]), p(lin["j_cv0"]), p(lin["j_cv1"]), self.lam, p(out.get("D")), p(out.get("E")),
-                    p(out.get("g")), p(out["delta"]), p(out["info"]), p(self.ws), self.ws.numel())
-            if self.prior is None:
+            fac = (self.T, self.L, self.n_kp, p(lin["r_proj"]), p(lin["j_proj"]), p(lin.get("status")),
+                   p(lin["r_dyn"]), p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]),
+                   p(lin["r_cv"]), p(lin["j_cv0"]), p(lin["j_cv1"]))
+            tail = (self.lam, p(out.get("D")), p(out.get("E")), p(out.get("g")), p(out["delta"]), p(out["info"]),
+                    p(self.ws), self.ws.numel())
+            args = fac + tail
+            if lin.get("r_cw") is not None:  # the factor on the angular velocity travels in `lin`
+                pr = self.prior
+                _lib.check(_lib.lib().pa_trajectory_gn_step_cw(
+                    *fac, p(lin["r_cw"]), p(lin["isig_cw"]), *tail, p(pr.info) if pr else None,
+                    p(pr.grad) if pr else None, _lib.stream_of(self.dev)), "pa_trajectory_gn_step_cw")
+            elif self.prior is None:
                 _lib.check(_lib.lib().pa_trajectory_gn_step(*args, _lib.stream_of(self.dev)), "pa_trajectory_gn_step")
             else:
                 _lib.check(_lib.lib().pa_trajectory_gn_step_prior(*args, p(self.prior.info), p(self.prior.grad),
@@ -269,11 +285,18 @@ class MarginalsPlan:
         """One pa_trajectory_marginals on the device's current stream."""
         lin, out, p = self.lin, self.out, _lib.ptr
         with torch.cuda.device(self.dev):
-            args = (self.T, self.L, self.n_kp, p(lin["r_proj"]), p(lin["j_proj"]), p(lin.get("status")),
-                    p(lin["r_dyn"]), p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]),
-                    p(lin["r_cv"]), p(lin["j_cv0"]), p(lin["j_cv1"]), self.lam, p(out.get("cov")), p(out.get("cross")),
-                    p(out.get("cov_newest")), p(out["info"]), p(self.ws), self.ws.numel())
-            if self.prior is None:
+            fac = (self.T, self.L, self.n_kp, p(lin["r_proj"]), p(lin["j_proj"]), p(lin.get("status")),
+                   p(lin["r_dyn"]), p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]),
+                   p(lin["r_cv"]), p(lin["j_cv0"]), p(lin["j_cv1"]))
+            tail = (self.lam, p(out.get("cov")), p(out.get("cross")), p(out.get("cov_newest")), p(out["info"]),
+                    p(self.ws), self.ws.numel())
+            args = fac + tail
+            if lin.get("r_cw") is not None:  # the factor on the angular velocity travels in `lin`
+                pr = self.prior
+                _lib.check(_lib.lib().pa_trajectory_marginals_cw(
+                    *fac, p(lin["r_cw"]), p(lin["isig_cw"]), *tail, p(pr.info) if pr else None,
+                    p(pr.grad) if pr else None, _lib.stream_of(self.dev)), "pa_trajectory_marginals_cw")
+            elif self.prior is None:
                 _lib.check(_lib.lib().pa_trajectory_marginals(*args, _lib.stream_of(self.dev)),
                            "pa_trajectory_marginals")
             else:
@@ -358,14 +381,17 @@ class PriorPlan:
         p, c, n = _lib.ptr, self.cur, self.nxt
         if n_kp is None:
             n_kp = lin["r_proj"].shape[0] // (self.T * self.L) if self.T * self.L and lin.get("r_proj") is not None else 0
+        fac = (self.T, self.L, n_kp, p(lin.get("r_proj")), p(lin.get("j_proj")), p(lin.get("status")), p(lin["r_dyn"]),
+               p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]), p(lin["r_cv"]),
+               p(lin["j_cv0"]), p(lin["j_cv1"]), p(c["info"]), p(self.grad))
+        tail = (float(lam), p(delta), p(gn_info), p(nvalid), p(pose), p(angvel), p(vel), p(n["info"]), p(n["eta"]),
+                p(n["xbar_pose"]), p(n["xbar_angvel"]), p(n["xbar_vel"]), p(self.minfo), _lib.stream_of(self.dev))
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib().pa_window_marginalize(
-                self.T, self.L, n_kp, p(lin.get("r_proj")), p(lin.get("j_proj")), p(lin.get("status")), p(lin["r_dyn"]),
-                p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]), p(lin["r_cv"]),
-                p(lin["j_cv0"]), p(lin["j_cv1"]), p(c["info"]), p(self.grad), float(lam), p(delta), p(gn_info),
-                p(nvalid), p(pose), p(angvel), p(vel), p(n["info"]), p(n["eta"]), p(n["xbar_pose"]),
-                p(n["xbar_angvel"]), p(n["xbar_vel"]), p(self.minfo), _lib.stream_of(self.dev)),
-                "pa_window_marginalize")
+            if lin.get("r_cw") is not None:  # the factor on the angular velocity travels in `lin`
+                _lib.check(_lib.lib().pa_window_marginalize_cw(*fac, p(lin["r_cw"]), p(lin["isig_cw"]), *tail),
+                           "pa_window_marginalize_cw")
+            else:
+                _lib.check(_lib.lib().pa_window_marginalize(*fac, *tail), "pa_window_marginalize")
 
     def advance(self) -> None:
         """The next prior becomes the current one: one device copy on the current stream (capturable;
@@ -454,7 +480,7 @@ class LMPlan:
 def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: int, dt: float, proj_sigmas, dyn_sigmas,
              cv_sigmas, nvalid: torch.Tensor | None = None, vel_frame: str = "world", camera_pose=None, H: int = 256,
              W: int = 256, newest_pending: bool = False, covariance: bool = False, cov_lambda: float = 1e-9,
-             proj_robust=None, prior=None, dt_pair=None, kp_mask=None, **params) -> dict:
+             proj_robust=None, prior=None, dt_pair=None, kp_mask=None, cw_sigmas=None, **params) -> dict:
     """Smoothed trajectories: Levenberg-Marquardt over all factors of T trajectories x L frames
     from the keypoints `y` (device) and the initial state, on the device (pa_trajectory_lm_solve;
     layouts as linearize_trajectories, the inputs are not modified).  Returns pose (T*L, 12),
@@ -470,13 +496,15 @@ def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: in
     prior (a PriorPlan): the marginalization prior on frame 0 (LMPlan); its grad / err are updated, and
     the covariance then has its Lambda in frame 0's block.
     dt_pair, kp_mask: as prepare_trajectories (a frame without any measured keypoint is held by its
-    dynamics factors alone; its rotation is then not observable, see include/perseus_amd.h)."""
+    dynamics factors alone; its rotation is then not observable unless cw_sigmas is given, see
+    include/perseus_amd.h).  cw_sigmas: as prepare_trajectories, the ConstantVelocityFactor on the angular
+    velocity; it enters the cost, every step and the covariance."""
     dev = y.device
     P, V, Wv = (_f64(a, dev).clone() for a in (poses, vels, angvels))  # updated in place: never the caller's
     a, lin = prepare_trajectories(y, P, V, Wv, corners, K, T=T, L=L, dt=dt, vel_frame=vel_frame,
                                   camera_pose=camera_pose, H=H, W=W, proj_sigmas=proj_sigmas, dyn_sigmas=dyn_sigmas,
                                   cv_sigmas=cv_sigmas, nvalid=nvalid, proj_robust=proj_robust, dt_pair=dt_pair,
-                                  kp_mask=kp_mask)
+                                  kp_mask=kp_mask, cw_sigmas=cw_sigmas)
     P, V, Wv = lin["_keep"][1:4]
     plan = LMPlan(a, lin, T=T, L=L, newest_pending=newest_pending, prior=prior, **params)
     plan.launch()

@@ -78,7 +78,13 @@ class StreamingPipeline:
     window_covariance() use them.  tick() / tick_keypoints() take stamps=, present= and kp_mask=;
     the new pair's dt and the new frame's mask go through one small pinned block [dt_new (n) f64 |
     mask_new (n) u32] that the graph copies to the device on the stream that runs the advance
-    (zero_copy: read in place), so one captured graph serves every tick.  Not with pre_ahead."""
+    (zero_copy: read in place), so one captured graph serves every tick.  Not with pre_ahead.
+    angvel_sigma (rad/s; None = off): the ConstantVelocityFactor on the ANGULAR velocity of every
+    frame pair (pipeline.prepare_trajectories cw_sigmas, pa_traj_args.r_cw), as GTSAM users put the
+    reference's factor on the angular-velocity keys: successive angular velocities are coupled, so a
+    frame without keypoints keeps an observable rotation.  It travels in the window's pa_traj_args
+    and factor outputs: every tick form, solve_window(), window_covariance(), marginalize=True and
+    timed=True honour it."""
 
     def __init__(self, model, n_cams: int = 3, src_hw=(720, 1280), bgr: bool = True, host_crop: bool = True,
                  graph: bool = True, near: float | None = None, far: float | None = None, device=None,
@@ -86,7 +92,9 @@ class StreamingPipeline:
                  proj_sigma: float = 1.0, dyn_sigma: float = 0.1, cv_sigma: float = 0.1, lam: float = 1e-2,
                  init_pose=None, init_vel=None, init_angvel=None, split_k: bool = True,
                  zero_copy: bool | None = None, split_pose: bool = True, pre_ahead: bool = False,
-                 zero_copy_out: bool = True, proj_robust=None, marginalize: bool = False, timed: bool = False):
+                 zero_copy_out: bool = True, proj_robust=None, marginalize: bool = False, timed: bool = False,
+                 angvel_sigma: float | None = None):
+        self.angvel_sigma = None if angvel_sigma is None else float(angvel_sigma)
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingPipeline needs a ROCm GPU (no CPU fallback)")
         if timed and pre_ahead:
@@ -360,7 +368,8 @@ class StreamingPipeline:
             self.win["y"].view(n * Lw, 2 * nk), self.win["pose"].view(n * Lw, 12), self.win["vel"].view(n * Lw, 3),
             self.win["angvel"].view(n * Lw, 3), corners, K, T=n, L=Lw, dt=self.dt, vel_frame=vel_frame, H=self.H,
             W=self.W, proj_sigmas=[proj_sigma] * 2, dyn_sigmas=[dyn_sigma] * 6, cv_sigmas=[cv_sigma] * 3,
-            nvalid=self.nvalid, proj_robust=proj_robust, **rings)
+            nvalid=self.nvalid, proj_robust=proj_robust,
+            cw_sigmas=None if self.angvel_sigma is None else [self.angvel_sigma] * 3, **rings)
         for k in ("y", "pose", "vel", "angvel"):  # linearize reads the window in place, no staging copy
             assert self.lin["_keep"][("y", "pose", "vel", "angvel").index(k)].data_ptr() == self.win[k].data_ptr()
         if self.timed:
