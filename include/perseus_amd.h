@@ -673,6 +673,73 @@ int pa_window_lm_prior_solve(const pa_traj_args* args, const pa_lm_params* p, in
                              int32_t* status_dev, double* lambda_dev, double* cost_hist_dev, void* ws_dev,
                              size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------- prediction and keypoint gate
+ * pa_window_predict: the newest state of every trajectory's window, predicted Q horizons ahead with
+ * the PoseDynamicsFactor model pa_window_advance predicts the new frame with, and its covariance.
+ * The state a prediction starts from is the one pa_window_advance starts from (see there): pose and
+ * velocity of frame L-1, the angular velocity of frame L-2 (frame L-1's enters no factor; L = 2:
+ * frame 1's).  Per trajectory t and query q, tau = tau[t*Q+q] seconds (device, not validated: a
+ * non-finite tau gives NaN outputs):
+ *   pose_out[t*Q+q] = T Exp(tau [w; v_b]),  v_b = R^T v for PA_VEL_WORLD,
+ * in the advance's operation order: for tau equal to the dt of an advance it is bit for bit the frame
+ * pa_window_advance_t predicts, for tau = 0 the input pose.
+ * Covariance (cov_out (T*Q, 12, 12) or NULL; needs cov and cross, pa_trajectory_marginals' outputs
+ * (T*L, 12, 12) and (T*(L-1), 12, 12), given together or both NULL, and then L >= 3): the predicted
+ * state is x' = [pose' (right perturbation, [omega; v]) | w | v], and to first order
+ *   F = [[-J0, -J1, -J2], [0, I, 0], [0, 0, I]],
+ * J0, J1, J2 the unwhitened PoseDynamicsFactor Jacobians at (T, w, v, pose2 = pose', dt = tau), where
+ * the residual is zero and J3 = I.  The input covariance Sigma* (12 x 12) is a principal sub-block of
+ * the window's full covariance: pose and velocity rows / columns from cov[L-1], the angular velocity
+ * block from cov[L-2][6:9, 6:9], the two coupled through cross[L-2][6:9, :]; the symmetric blocks are
+ * read from their upper triangles.
+ *   cov_out = F Sigma* F^T + diag(q_diag),
+ * q_diag (12, device, or NULL = none) process-noise variances; every block is exactly symmetric.
+ * cov_info (T) or NULL: pa_trajectory_marginals' info; a trajectory with cov_info != 0 gets NaN in
+ * cov_out (its poses are still predicted).
+ * PA_EINVAL before any launch: T < 0, Q < 1, L < 2; exactly one of cov / cross; cov_out without
+ * them; cov with L < 3; a bad vel_frame; a NULL pose, angvel, vel, tau or pose_out.  T = 0 is a
+ * no-op.  One launch (one lane per (t, q)), no host synchronisation (capturable). */
+int pa_window_predict(int T, int L, int Q, const double* pose, const double* angvel, const double* vel,
+                      const double* cov, const double* cross, const int32_t* cov_info, const double* q_diag,
+                      const double* tau, int vel_frame, double* pose_out, double* cov_out, void* stream);
+
+/* pa_keypoint_gate: an innovation (chi-square) test of the detector's keypoints against a predicted
+ * pose, clearing the mask bits (pa_traj_args.kp_mask / mask_new) of the corners that fail it.
+ * Inputs per trajectory t: y_new (T, 2K) f32 normalized keypoints; the predicted pose at
+ * pose_pred + t*pose_stride (doubles, pose_stride >= 12); cov_pred (T, 12, 12), of which the 6 x 6
+ * pose block P is used (pa_window_predict's cov_out); corners, K, tcam (NULL = identity) and
+ * isig_proj (2, required: the inverse pixel sigmas) as in pa_traj_args; the mask word at
+ * mask + t*mask_stride (mask_stride >= 1), in and out.  Both strides exist so that the gate can act
+ * on the new-frame block (mask_new, strides 1 and 12) before a fused tick, or on the ring entry
+ * kp_mask[t*L + L-1] (mask stride L, pose stride 12 L) between the two halves of a split tick.
+ * Per keypoint k < n_kp whose bit is set in the incoming word: z = the pixel of y_new (f32 kornia
+ * denormalize, as pa_trajectory_linearize); (zhat, H 2 x 6) the unwhitened KeypointProjectionFactor
+ * at the predicted pose; S = H P H^T + diag(sigma_u^2, sigma_v^2); d2 = (zhat - z)^T S^-1 (zhat - z)
+ * by the closed 2 x 2 form.  The keypoint passes iff there is no cheirality at the predicted pose, S
+ * is finite with a positive determinant, and d2 <= chi2; d2 is NaN where it could not be formed.
+ * Outputs: the mask word & the pass bits below n_kp (bits at and above n_kp are copied through);
+ * d2 (T, K) or NULL, NaN for a bit that came in cleared; zhat (T, K, 2) or NULL, the predicted pixel
+ * of every corner whatever its bit (NaN on cheirality); ginfo (T, required).
+ * The gate abstains -- the mask word is left as it came -- and says why in ginfo, the first reason
+ * in this order winning:
+ *   PA_GATE_YOUNG   nvalid[t] < min_frames (nvalid (T) or NULL = never young); d2 NaN
+ *   PA_GATE_NOCOV   a non-finite entry in P; d2 NaN
+ *   PA_GATE_FEW     fewer than min(min_pass, popcount(incoming word's bits below n_kp)) keypoints
+ *                   pass (a lost track: without it a track whose every corner is gated could never
+ *                   recover); d2 still written
+ *   PA_GATE_APPLIED otherwise.
+ * PA_EINVAL before any launch: T < 0; n_kp outside [1, 32]; chi2 not a positive finite number;
+ * min_pass < 0; pose_stride < 12; mask_stride < 1; a NULL required pointer.  T = 0 is a no-op.
+ * One launch (32 lanes per trajectory, corner k on lane k), no host synchronisation (capturable). */
+#define PA_GATE_APPLIED 0
+#define PA_GATE_FEW 1
+#define PA_GATE_NOCOV 2
+#define PA_GATE_YOUNG 3
+int pa_keypoint_gate(int T, int n_kp, int H, int W, const float* y_new, const double* pose_pred, long pose_stride,
+                     const double* cov_pred, const double* corners, const double* K, const double* tcam,
+                     const double* isig_proj, double chi2, int min_pass, const int32_t* nvalid, int min_frames,
+                     uint32_t* mask, long mask_stride, double* d2, double* zhat, int32_t* ginfo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,11 @@ LM_CONVERGED = 1
 LM_MAX_ITERS = 2
 LM_STALLED = 3
 
+GATE_APPLIED = 0
+GATE_FEW = 1
+GATE_NOCOV = 2
+GATE_YOUNG = 3
+
 # name -> (restype, argtypes)
 _SIGS = {
     "pa_trajectory_lm_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -153,6 +158,10 @@ _SIGS = {
                                                                                        C.c_void_p]),
     "pa_window_advance_t": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_double, C.c_int,
                                                                                         C.c_void_p]),
+    "pa_window_predict": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 3),
+    "pa_keypoint_gate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
+                         + [C.c_void_p] * 5 + [C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_long]
+                         + [C.c_void_p] * 4),
     "pa_window_retract": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 6),
     "pa_debug_gn_set_assemblers": (C.c_int, [C.c_int]),
     "pa_window_retract_newest": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 7),

@@ -624,3 +624,133 @@ def window_retract(win: dict, delta: torch.Tensor, info: torch.Tensor | None = N
                                                        win["angvel"].data_ptr(), win["vel"].data_ptr(),
                                                        _lib.ptr(newest), _lib.stream_of(dev)),
                    "pa_window_retract")
+
+
+def _vel_code(vel_frame: str) -> int:
+    if vel_frame not in ("world", "body"):
+        raise AssertionError("vel_frame must be 'world' or 'body'.")  # factors.py:41
+    return _lib.VEL_WORLD if vel_frame == "world" else _lib.VEL_BODY
+
+
+class PredictPlan:
+    """The newest state of every window predicted Q horizons ahead, with its covariance
+    (pa_window_predict): the PoseDynamicsFactor model pa_window_advance predicts the new frame with,
+    from pose and velocity of frame L-1 and the angular velocity of frame L-2.  win: the window dict
+    (pose (T, L, 12), angvel / vel (T, L, 3), device f64, read in place at every launch).  marg
+    (optional): a MarginalsPlan(cross=True) over the same windows; its cov, cross and info feed the
+    covariance cov_out = F Sigma* F^T + diag(q_diag) (include/perseus_amd.h), NaN for a trajectory
+    whose marginals failed.  q_diag (optional, 12 variances: [pose 6 | angvel 3 | vel 3]).  Buffers
+    are allocated once, so `launch` can be captured in a HIP graph and replayed.
+    tau (T, Q) f64 device, seconds: fill it before a launch, or pass tau= (a device tensor or
+    address of T*Q doubles read in place, e.g. a tick's dt_new with Q = 1).
+    out: pose (T, Q, 12) and, with marg, cov (T, Q, 12, 12)."""
+
+    def __init__(self, win: dict, *, Q: int = 1, marg=None, q_diag=None, vel_frame: str = "world", tau=None):
+        T, L = win["pose"].shape[:2]
+        dev = win["pose"].device
+        if marg is not None and (marg.out.get("cov") is None or marg.out.get("cross") is None):
+            raise ValueError("PredictPlan: the covariance needs a MarginalsPlan(full=True, cross=True)")
+        self.T, self.L, self.Q, self.win, self.marg, self.dev = T, L, int(Q), win, marg, dev
+        self.vel_frame = _vel_code(vel_frame)
+        self.q_diag = _f64(q_diag, dev, (12,))
+        self.tau = torch.zeros((T, self.Q), dtype=torch.float64, device=dev) if tau is None else tau
+        self.out = {"pose": torch.empty((T, self.Q, 12), dtype=torch.float64, device=dev)}
+        if marg is not None:
+            self.out["cov"] = torch.empty((T, self.Q, 12, 12), dtype=torch.float64, device=dev)
+
+    def launch(self) -> None:
+        """One pa_window_predict on the device's current stream."""
+        p, w, m = _lib.ptr, self.win, self.marg
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().pa_window_predict(
+                self.T, self.L, self.Q, p(w["pose"]), p(w["angvel"]), p(w["vel"]),
+                p(m.out["cov"]) if m else None, p(m.out["cross"]) if m else None, p(m.out["info"]) if m else None,
+                p(self.q_diag), p(self.tau), self.vel_frame, p(self.out["pose"]), p(self.out.get("cov")),
+                _lib.stream_of(self.dev)), "pa_window_predict")
+
+
+class GatePlan:
+    """The chi-square gate of the detector's keypoints against a predicted pose (pa_keypoint_gate):
+    a corner whose innovation d2 exceeds chi2 under S = H P H^T + diag(sigma^2) loses its mask bit.
+    y (T, 2K) f32 device keypoints; pose_pred / cov_pred: device tensors (or addresses) of the
+    predicted poses (stride pose_stride doubles per trajectory) and covariances (T, 12, 12), e.g. a
+    PredictPlan's outputs with Q = 1; corners (K, 3), K (5), isig_proj (2), tcam (12 or None): device
+    f64 tensors, as prepare_trajectories stages them; mask: int32 device tensor or address of the
+    words gated in place, word t at mask + t*mask_stride; nvalid (optional, int32 (T,)).  Outputs
+    are allocated once, `launch` is capturable.  out: d2 (T, K), zhat (T, K, 2), ginfo (T,) int32
+    (_lib.GATE_APPLIED / GATE_FEW / GATE_NOCOV / GATE_YOUNG: everything but APPLIED leaves the
+    word as it came)."""
+
+    def __init__(self, y: torch.Tensor, pose_pred, cov_pred, corners, K, isig_proj, mask, *, chi2: float,
+                 min_pass: int = 4, min_frames: int = 3, nvalid=None, tcam=None, H: int = 256, W: int = 256,
+                 pose_stride: int = 12, mask_stride: int = 1):
+        T, ny = y.shape
+        dev = y.device
+        self.T, self.n_kp, self.H, self.W, self.dev = T, ny // 2, int(H), int(W), dev
+        self.y, self.pose_pred, self.cov_pred, self.mask, self.nvalid = y, pose_pred, cov_pred, mask, nvalid
+        self.corners, self.K, self.isig_proj, self.tcam = corners, K, isig_proj, tcam
+        self.chi2, self.min_pass, self.min_frames = float(chi2), int(min_pass), int(min_frames)
+        self.pose_stride, self.mask_stride = int(pose_stride), int(mask_stride)
+        self.out = {"d2": torch.empty((T, self.n_kp), dtype=torch.float64, device=dev),
+                    "zhat": torch.empty((T, self.n_kp, 2), dtype=torch.float64, device=dev),
+                    "ginfo": torch.empty(T, dtype=torch.int32, device=dev)}
+
+    def launch(self) -> None:
+        """One pa_keypoint_gate on the device's current stream."""
+        p, o = _lib.ptr, self.out
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().pa_keypoint_gate(
+                self.T, self.n_kp, self.H, self.W, p(self.y), p(self.pose_pred), self.pose_stride, p(self.cov_pred),
+                p(self.corners), p(self.K), p(self.tcam), p(self.isig_proj), self.chi2, self.min_pass,
+                p(self.nvalid), self.min_frames, p(self.mask), self.mask_stride, p(o["d2"]), p(o["zhat"]),
+                p(o["ginfo"]), _lib.stream_of(self.dev)), "pa_keypoint_gate")
+
+
+def predict(win: dict, taus, *, cov=None, cross=None, cov_info=None, q_diag=None, vel_frame: str = "world") -> dict:
+    """pa_window_predict, eagerly: the newest state of every window in `win` (pose (T, L, 12), angvel /
+    vel (T, L, 3), device) at the horizons taus ((Q,) shared by every trajectory, or (T, Q), seconds).
+    cov / cross (optional, together): pa_trajectory_marginals' outputs (`marginals(..., cross=True)`),
+    with cov_info its info.  Returns pose (T, Q, 12) and, with cov, cov (T, Q, 12, 12)."""
+    T, L = win["pose"].shape[:2]
+    dev = win["pose"].device
+    tau = torch.as_tensor(np.asarray(taus, np.float64), device=dev)
+    tau = (tau.reshape(1, -1).expand(T, -1) if tau.dim() < 2 else tau.reshape(T, -1)).contiguous()
+    if (cov is None) != (cross is None):
+        raise ValueError("predict: cov and cross are given together")
+    marg = None
+    if cov is not None:
+        class _Marg:  # (the three tensors a MarginalsPlan would hold)
+            out = {"cov": _f64(cov, dev, (T * L, 12, 12)), "cross": _f64(cross, dev, (T * (L - 1), 12, 12)),
+                   "info": None if cov_info is None else cov_info.to(device=dev, dtype=torch.int32).contiguous()}
+        marg = _Marg
+    w = {k: _f64(win[k], dev) for k in ("pose", "angvel", "vel")}
+    plan = PredictPlan(w, Q=tau.shape[1], marg=marg, q_diag=q_diag, vel_frame=vel_frame, tau=tau)
+    plan.launch()
+    out = dict(plan.out)
+    out["_keep"] = (w, tau, marg, plan.q_diag)
+    return out
+
+
+def gate_keypoints(y: torch.Tensor, pose_pred, cov_pred, corners, K, proj_sigmas, mask, *, chi2: float,
+                   min_pass: int = 4, min_frames: int = 3, nvalid=None, camera_pose=None, H: int = 256,
+                   W: int = 256) -> dict:
+    """pa_keypoint_gate, eagerly: y (T, 2K) device keypoints against pose_pred (T, 12) with cov_pred
+    (T, 12, 12); mask (T,) ints (one bit per keypoint) is staged, not modified.  Returns mask (T,)
+    int32 (the gated words), d2 (T, K), zhat (T, K, 2) and ginfo (T,) int32."""
+    if y.device.type != "cuda":
+        raise RuntimeError("gate_keypoints expects the detector output on the GPU (no CPU fallback)")
+    dev = y.device
+    y = y.to(torch.float32).contiguous()
+    T, nk = y.shape[0], y.shape[1] // 2
+    m = _mask(mask, dev, (T,)).clone()
+    keep = (_f64(pose_pred, dev, (T, 12)), _f64(cov_pred, dev, (T, 12, 12)), _f64(corners, dev, (nk, 3)),
+            _f64(K, dev, (5,)), _isig(proj_sigmas, 2, dev), _f64(camera_pose, dev, (12,)))
+    nv = None if nvalid is None else torch.as_tensor(np.asarray(nvalid, np.int32), device=dev) \
+        if not isinstance(nvalid, torch.Tensor) else nvalid.to(device=dev, dtype=torch.int32).contiguous()
+    plan = GatePlan(y, keep[0], keep[1], keep[2], keep[3], keep[4], m, chi2=chi2, min_pass=min_pass,
+                    min_frames=min_frames, nvalid=nv, tcam=keep[5], H=H, W=W)
+    plan.launch()
+    out = dict(plan.out)
+    out["mask"] = m
+    out["_keep"] = (y, keep, nv)
+    return out

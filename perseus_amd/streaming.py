@@ -84,7 +84,25 @@ class StreamingPipeline:
     reference's factor on the angular-velocity keys: successive angular velocities are coupled, so a
     frame without keypoints keeps an observable rotation.  It travels in the window's pa_traj_args
     and factor outputs: every tick form, solve_window(), window_covariance(), marginalize=True and
-    timed=True honour it."""
+    timed=True honour it.
+    gate_chi2 (None = off; needs timed=True, else ValueError): the chi-square gate that fills in
+    kp_mask.  Every tick, inside the captured graph: the window's marginals with their cross blocks
+    (pipeline.MarginalsPlan over the factor outputs as they stand when the tick starts: the last
+    tick's linearization, the one window_covariance() reports, with the tick's lam, the prior and the
+    factor on the angular velocity where they are on), pa_window_predict to this tick's dt_new with one
+    factor's worth of process noise (dyn_sigma^2 on the pose, angvel_sigma^2 or 0, cv_sigma^2), and
+    pa_keypoint_gate on the detector's keypoints: a corner whose innovation exceeds gate_chi2 (13.816
+    = the 0.999 quantile at 2 degrees of freedom) loses its bit.  The effective mask, the staged one
+    AND the gate, is what the tick sees and what lands in win["mask"][:, -1].  The gate abstains while
+    the window holds fewer than gate_min_frames real frames, while the covariance is not finite, and
+    when fewer than gate_min_pass corners pass (a lost track must be able to recover); gate_state()
+    reports d2, ginfo and the effective mask.  With the gate on, dt_new / mask_new are copied to the
+    device every tick (not read zero-copy), because the fused tick's gate writes the copy.  The
+    covariance is taken at the last tick's linearization point while the state is the retracted one,
+    as window_covariance()'s is.  The gate is only as sharp as the model's own noise: with dyn_sigma =
+    0.1 the prediction is uncertain by about 0.1 m and a corner 40 px off passes; gating such corners
+    needs a dyn_sigma of a few mm / mrad.  That is a property of the model, not a defect of the gate.
+    predict(taus): the newest pose with its covariance at horizons after the newest frame."""
 
     def __init__(self, model, n_cams: int = 3, src_hw=(720, 1280), bgr: bool = True, host_crop: bool = True,
                  graph: bool = True, near: float | None = None, far: float | None = None, device=None,
@@ -93,8 +111,21 @@ class StreamingPipeline:
                  init_pose=None, init_vel=None, init_angvel=None, split_k: bool = True,
                  zero_copy: bool | None = None, split_pose: bool = True, pre_ahead: bool = False,
                  zero_copy_out: bool = True, proj_robust=None, marginalize: bool = False, timed: bool = False,
-                 angvel_sigma: float | None = None):
+                 angvel_sigma: float | None = None, gate_chi2: float | None = None, gate_min_pass: int = 4,
+                 gate_min_frames: int = 3):
         self.angvel_sigma = None if angvel_sigma is None else float(angvel_sigma)
+        self.gate_chi2 = None if gate_chi2 is None else float(gate_chi2)
+        self.gate_min_pass, self.gate_min_frames = int(gate_min_pass), int(gate_min_frames)
+        self._gate = None
+        if self.gate_chi2 is not None:
+            if not timed:
+                raise ValueError("StreamingPipeline: gate_chi2 needs timed=True (the gate writes the keypoint masks)")
+            if not (np.isfinite(self.gate_chi2) and self.gate_chi2 > 0) or self.gate_min_pass < 0:
+                raise ValueError(f"StreamingPipeline: gate_chi2 must be a positive finite number and gate_min_pass "
+                                 f">= 0, got {gate_chi2}, {gate_min_pass}")
+            if 0 < pose_window < 3:
+                raise ValueError("StreamingPipeline: gate_chi2 needs pose_window >= 3 (the prediction's covariance "
+                                 "takes frame L-2's angular velocity)")
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingPipeline needs a ROCm GPU (no CPU fallback)")
         if timed and pre_ahead:
@@ -287,15 +318,33 @@ class StreamingPipeline:
     def _enqueue_timed_in(self):
         """timed: this tick's [dt_new | mask_new] to the device, on the stream that runs the advance
         and before it (one 12 n byte copy; zero_copy: nothing, the advance reads the pinned block)."""
-        if self.timed and not self.zero_copy:
+        if self.timed and (not self.zero_copy or self._gate is not None):
             self.tm_d.copy_(self.tm_h, non_blocking=True)
+
+    def _enqueue_gate_predict(self):
+        """gate: the marginals of the window as the tick finds it (the last tick's linearization and
+        prior, so before _enqueue_prior_in and before the tick overwrites the factor outputs), the
+        prediction to this tick's dt_new (after _enqueue_timed_in), and nvalid before the advance."""
+        if self._gate is not None:
+            marg, pred, _ = self._gate
+            self._gate_nvalid.copy_(self.nvalid)
+            marg.launch()
+            pred.launch()
+
+    def _enqueue_gate(self):
+        """gate: the detector's keypoints (self.y) against the prediction; clears bits of the new
+        frame's mask word before the launch that reads it."""
+        if self._gate is not None:
+            self._gate[2].launch()
 
     def _enqueue_pose_pre(self):
         self._enqueue_timed_in()
+        self._enqueue_gate_predict()
         self._enqueue_prior_in()
         pipeline.window_pose_tick_pre(self.traj_args, self.tick_ws, lam=self.gn.lam, prior=self.prior)
 
     def _enqueue_pose_post(self):
+        self._enqueue_gate()  # (on the ring entry the pre half landed)
         if self._zc_out:  # info and the newest poses straight into the pinned output block
             info, newest = self._out_dev + self._px_bytes, self._out_dev + self._po
         else:
@@ -315,6 +364,8 @@ class StreamingPipeline:
             self._enqueue_pose_post()
             return
         self._enqueue_timed_in()
+        self._enqueue_gate_predict()
+        self._enqueue_gate()  # (on the device copy of mask_new, before the advance reads it)
         self._enqueue_prior_in()
         if self.fused_pose:
             pipeline.window_pose_tick(self.traj_args, self.y, lam=self.gn.lam, delta=self.gn.out["delta"],
@@ -376,7 +427,7 @@ class StreamingPipeline:
             assert self.traj_args.dt_pair == self.win["dt"].data_ptr()
             assert self.traj_args.kp_mask == self.win["mask"].data_ptr()
             base = self.tm_d.data_ptr()
-            if self.zero_copy:
+            if self.zero_copy and self.gate_chi2 is None:  # (the gate writes the device copy's masks)
                 dp = C.c_void_p()
                 _lib.check(_lib.lib().pa_host_device_pointer(C.c_void_p(self.tm_h.data_ptr()), C.byref(dp)),
                            "host_device_pointer")
@@ -411,6 +462,35 @@ class StreamingPipeline:
             self.gn.out["info"] = None
         self.tick_ws = pipeline.window_pose_tick_workspace(n, Lw, dev)
         self.side = torch.cuda.Stream(dev)
+        self._sigmas = (float(dyn_sigma), float(cv_sigma))
+        self._pred = None  # predict()'s plans, built on first use
+        if self.gate_chi2 is not None:
+            # the gate's three launches.  Marginals and prediction read the window and the factor
+            # outputs as the tick finds them; the gate itself acts on the new frame's mask word: the
+            # ring entry the pre half has landed (split tick: strides L and 12 L, the predicted pose is
+            # the advanced window's newest frame), or the device copy of mask_new (fused / four-launch)
+            marg = pipeline.MarginalsPlan(self.lin, T=n, L=Lw, lam=lam, cross=True, prior=self.prior)
+            self._gate_nvalid = torch.zeros(n, dtype=torch.int32, device=dev)  # nvalid as the tick starts
+            pred = pipeline.PredictPlan(self.win, Q=1, marg=marg, q_diag=self._process_noise(), vel_frame=vel_frame,
+                                        tau=self._tm_ptrs[0])
+            _, _, _, _, Cn, Kt, Tc, isp = self.lin["_keep"][:8]
+            if self.split_pose:
+                tgt = dict(pose_pred=self.win["pose"].data_ptr() + (Lw - 1) * 12 * 8, pose_stride=12 * Lw,
+                           mask=self.win["mask"].data_ptr() + (Lw - 1) * 4, mask_stride=Lw)
+            else:
+                tgt = dict(pose_pred=pred.out["pose"], pose_stride=12, mask=self._tm_ptrs[1], mask_stride=1)
+            gate = pipeline.GatePlan(self.y, tgt.pop("pose_pred"), pred.out["cov"], Cn, Kt, isp, tgt.pop("mask"),
+                                     chi2=self.gate_chi2, min_pass=self.gate_min_pass,
+                                     min_frames=self.gate_min_frames, nvalid=self._gate_nvalid, tcam=Tc, H=self.H,
+                                     W=self.W, **tgt)
+            self._gate = (marg, pred, gate)
+
+    def _process_noise(self) -> torch.Tensor:
+        """One factor's worth of process noise, [dyn_sigma^2 x 6 | angvel_sigma^2 or 0 x 3 | cv_sigma^2
+        x 3]: the graph's dynamics noise is per frame pair, not per second."""
+        sd, sc = self._sigmas
+        sw = 0.0 if self.angvel_sigma is None else self.angvel_sigma
+        return torch.tensor([sd * sd] * 6 + [sw * sw] * 3 + [sc * sc] * 3, dtype=torch.float64, device=self.dev)
 
     def reset_window(self) -> None:
         """Every frame of every camera's window back to the initial state (keypoints 0, no
@@ -511,6 +591,54 @@ class StreamingPipeline:
         self.stream.synchronize()
         return {"cov": self._marg.out["cov"].view(self.n, self.pose_L, 12, 12).cpu().numpy().copy(),
                 "info": self._marg.out["info"].cpu().numpy().copy()}
+
+    def gate_state(self) -> dict:
+        """The last tick's gate (gate_chi2), per camera, as numpy: d2 (n, K) the innovations' squared
+        Mahalanobis distances (NaN for a corner that came in masked, that could not be tested, or
+        when the gate was too young or had no covariance), ginfo (n,) int32 (_lib.GATE_APPLIED = 0,
+        GATE_FEW = 1, GATE_NOCOV = 2, GATE_YOUNG = 3; non-zero: the staged mask went through as it
+        came) and mask (n,) int32, the effective mask the tick used (win["mask"][:, -1]).
+        Synchronises the pipeline's stream."""
+        if self._gate is None:
+            raise RuntimeError("gate_state() needs a pipeline built with gate_chi2")
+        self.stream.synchronize()
+        out = self._gate[2].out
+        return {"d2": out["d2"].cpu().numpy().copy(), "ginfo": out["ginfo"].cpu().numpy().copy(),
+                "mask": self.win["mask"][:, -1].cpu().numpy().copy()}
+
+    def predict(self, taus, process_noise: bool = True) -> tuple:
+        """The latency-compensated output: every camera's newest pose predicted to the horizons taus
+        ((Q,) seconds after the newest frame's stamp) with the PoseDynamicsFactor model, and its
+        covariance (pipeline.PredictPlan, pa_window_predict): poses (n, Q, 12) and covariances
+        (n, Q, 12, 12) of [pose (6, right perturbation, [omega; v]) | angvel (3) | vel (3)], numpy.
+        The covariance propagates window_covariance()'s marginals (the last tick's linearization,
+        the tick's lam, the prior and the factor on the angular velocity where they are on) to first
+        order; process_noise adds one factor's worth of it, whatever the horizon (dyn_sigma^2 on the
+        pose, angvel_sigma^2 or 0, cv_sigma^2: the graph's dynamics noise is per frame pair).  NaN
+        covariances for a camera whose marginals failed.  Runs eagerly on the pipeline's stream,
+        outside the captured tick graph.  With pre_ahead the window between ticks already belongs
+        to the next tick: ValueError."""
+        if not self.pose_L:
+            raise RuntimeError("predict() needs the pose stage (pose_window > 0)")
+        if self.pre_ahead:
+            raise ValueError("predict(): with pre_ahead=True the window between ticks is already the next tick's "
+                             "(advanced, its newest frame a prediction itself)")
+        if self.pose_L < 3:
+            raise ValueError("predict(): the covariance needs pose_window >= 3")
+        tau = np.asarray(taus, np.float64).reshape(-1)
+        if self._pred is None or self._pred[1].Q != len(tau):
+            marg = pipeline.MarginalsPlan(self.lin, T=self.n, L=self.pose_L, lam=self.gn.lam, cross=True,
+                                          prior=self.prior)
+            self._pred = (marg, pipeline.PredictPlan(self.win, Q=len(tau), marg=marg, vel_frame=self.vel_frame),
+                          self._process_noise())
+        marg, pred, q = self._pred
+        pred.q_diag = q if process_noise else None
+        with torch.cuda.stream(self.stream):
+            pred.tau.copy_(torch.as_tensor(tau).reshape(1, -1).expand(self.n, -1))
+            marg.launch()
+            pred.launch()
+        self.stream.synchronize()
+        return pred.out["pose"].cpu().numpy().copy(), pred.out["cov"].cpu().numpy().copy()
 
     def stage(self, rgb: np.ndarray, depth: np.ndarray | None = None) -> None:
         """Copy one tick of camera frames (n, Hs, Ws, 3) uint8 + (n, Hs, Ws) f32 metres

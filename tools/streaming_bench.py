@@ -7,6 +7,12 @@ also window advance, factor linearize, GN step, retract, D2H poses), wait.  Prin
 JSON line.
 
     python tools/streaming_bench.py [--ticks 300] [--hz 30] [--window 24] [--channels {3,4}] [--timed 1]
+                                      [--gate CHI2]
+
+--gate CHI2 (only with --timed 1; default off) switches the keypoint gate on (StreamingPipeline(
+gate_chi2=CHI2): the window's marginals, pa_window_predict and pa_keypoint_gate inside the tick's
+graph), so the tick latency can be read with and without it; the report gains "gate_chi2" and the
+number of cameras whose gate applied on the last tick.
 
 --timed 1 runs the pose tick with real timestamps (StreamingPipeline(timed=True)): seeded +-30 %
 stamp jitter per camera, the same report fields for the one mode "pose".
@@ -23,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def timed_leg(model, dev, ticks, hz, cams, window, zero_copy, zero_copy_out, seed=0, jitter=0.3):
+def timed_leg(model, dev, ticks, hz, cams, window, zero_copy, zero_copy_out, seed=0, jitter=0.3, gate=None):
     """bench.streaming_leg's "pose" mode with StreamingPipeline(timed=True): every tick is given
     per-camera stamps with seeded +-`jitter` period jitter (the pacing itself stays at `hz`), so
     the tick stages and copies its [dt_new | mask_new] block.  The same report fields.
@@ -42,7 +48,8 @@ def timed_leg(model, dev, ticks, hz, cams, window, zero_copy, zero_copy_out, see
     rgbs = rng.integers(0, 256, (n_src, cams, 720, 1280, 3), dtype=np.uint8)
     deps = rng.uniform(0.12, 0.48, (n_src, cams, 720, 1280)).astype(np.float32)
     pipe = StreamingPipeline(model, n_cams=cams, graph=True, host_crop=True, device=dev, zero_copy=zero_copy,
-                             zero_copy_out=zero_copy_out, pose_window=window, proj_sigma=40.0, timed=True)
+                             zero_copy_out=zero_copy_out, pose_window=window, proj_sigma=40.0, timed=True,
+                             gate_chi2=gate)
     jr = np.random.default_rng(seed)
     period = 1.0 / hz
     stamps = np.zeros(cams)
@@ -77,6 +84,8 @@ def timed_leg(model, dev, ticks, hz, cams, window, zero_copy, zero_copy_out, see
          "device_ms_per_tick": round(e0.elapsed_time(e1) / 20, 4), "window_frames": window,
          "precision": pipe.model.precision, "timed": True, "stamp_jitter": jitter,
          "solved_last_tick": int((pipe.info_h.numpy() == 0).sum())}
+    if gate is not None:
+        r.update(gate_chi2=gate, gate_applied_last_tick=int((pipe.gate_state()["ginfo"] == 0).sum()))
     pipe.close()
     return {"workload": f"configs[4]: {cams} x 720p RGBD @ {hz:g} Hz, centre crop 256, B = {cams} per tick, timed",
             "unit": "ms", "timing": "host time from staging start to results on the host, paced ticks", "pose": r}
@@ -94,7 +103,11 @@ def main():
                    help="3: the RGB model (the tick stages and reads the colour frames alone; fp16 modes only)")
     p.add_argument("--timed", type=int, default=0,
                    help="1: the pose tick with real timestamps (StreamingPipeline(timed=True)), seeded +-30 %% stamp jitter")
+    p.add_argument("--gate", type=float, default=None, metavar="CHI2",
+                   help="the keypoint gate's chi-square bound (e.g. 13.816); needs --timed 1; default: no gate")
     a = p.parse_args()
+    if a.gate is not None and not a.timed:
+        p.error("--gate needs --timed 1 (the gate writes the keypoint masks)")
     import numpy as np
     import torch
 
@@ -108,7 +121,8 @@ def main():
     dev = torch.device("cuda", 0)
     if a.timed:
         print(json.dumps(timed_leg(m, dev, a.ticks, a.hz, a.cams, a.window,
-                                   None if a.zero_copy is None else bool(a.zero_copy), bool(a.zero_copy_out))))
+                                   None if a.zero_copy is None else bool(a.zero_copy), bool(a.zero_copy_out),
+                                   gate=a.gate)))
         return
     kw = {}
     if a.channels == 3:  # (the leg's parity modes build their own 4-channel fp16x3 model)
