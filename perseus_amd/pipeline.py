@@ -59,6 +59,32 @@ def _isig(sigmas, dim, dev):
     return torch.as_tensor(1.0 / s, device=dev).contiguous()
 
 
+def _empty(dev):
+    """e(*shape, dtype=f64): an uninitialised tensor on dev."""
+    def e(*shape, dtype=torch.float64):
+        return torch.empty(shape, dtype=dtype, device=dev)
+    return e
+
+
+def _vel_code(vel_frame: str) -> int:
+    if vel_frame not in ("world", "body"):
+        raise AssertionError("vel_frame must be 'world' or 'body'.")  # factors.py:41
+    return _lib.VEL_WORLD if vel_frame == "world" else _lib.VEL_BODY
+
+
+def _factor_args(lin: dict, T: int, L: int, n_kp: int) -> tuple:
+    """(T, L, n_kp, then the 11 factor-output pointers) as pa_trajectory_gn_step_cw, pa_trajectory_marginals_cw
+    and pa_window_marginalize_cw take them first (projection outputs may be absent with n_kp = 0)."""
+    return (T, L, n_kp) + tuple(_lib.ptr(lin.get(k)) for k in (
+        "r_proj", "j_proj", "status", "r_dyn", "j_dyn0", "j_dyn1", "j_dyn2", "j_dyn3", "r_cv", "j_cv0", "j_cv1"))
+
+
+def _entry(base: str, lin: dict, prior) -> str:
+    """The name of the narrowest C entry point that takes these arguments: what an error is reported
+    under.  The call itself goes to the widest sibling, whose NULL arguments make it the narrower ones."""
+    return base + ("_cw" if lin.get("r_cw") is not None else "_prior" if prior is not None else "")
+
+
 def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: int, dt: float,
                          vel_frame: str = "world", camera_pose=None, H: int = 256, W: int = 256,
                          proj_sigmas=None, dyn_sigmas=None, cv_sigmas=None, jacobians: bool = True,
@@ -86,8 +112,7 @@ def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T
     LMPlan and the streaming ticks honour the factor when `out` / `args` carry it.  None: off."""
     if y.device.type != "cuda":
         raise RuntimeError("linearize_trajectories expects the detector output on the GPU (no CPU fallback)")
-    if vel_frame not in ("world", "body"):
-        raise AssertionError("vel_frame must be 'world' or 'body'.")  # factors.py:41
+    vel_code = _vel_code(vel_frame)
     dev = y.device
     F = T * L
     y = y.to(torch.float32).contiguous()
@@ -103,10 +128,7 @@ def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T
     isp, isd, isc = _isig(proj_sigmas, 2, dev), _isig(dyn_sigmas, 6, dev), _isig(cv_sigmas, 3, dev)
     isw = _isig(cw_sigmas, 3, dev)
     n, m = F * nk, T * max(L - 1, 0)
-
-    def e(*shape, dtype=torch.float64):
-        return torch.empty(shape, dtype=dtype, device=dev)
-
+    e = _empty(dev)
     out = {"r_proj": e(n, 2), "status": e(n, dtype=torch.int32), "err_proj": e(n) if isp is not None or proj_robust is not None else None,
            "r_dyn": e(m, 6), "err_dyn": e(m) if isd is not None else None,
            "r_cv": e(m, 3), "err_cv": e(m) if isc is not None else None}
@@ -118,7 +140,7 @@ def prepare_trajectories(y: torch.Tensor, poses, vels, angvels, corners, K, *, T
     a.y, a.pose, a.vel, a.angvel, a.corners, a.K = (t.data_ptr() for t in (y, P, V, Wv, Cn, Kt))
     a.tcam = _lib.ptr(Tc)
     a.dt = float(dt)
-    a.vel_frame = _lib.VEL_WORLD if vel_frame == "world" else _lib.VEL_BODY
+    a.vel_frame = vel_code
     a.isig_proj, a.isig_dyn, a.isig_cv = _lib.ptr(isp), _lib.ptr(isd), _lib.ptr(isc)
     if isw is not None:  # the factor on the angular velocity: r_cw is its switch
         out["r_cw"], out["err_cw"], out["isig_cw"] = e(m, 3), e(m), isw
@@ -194,10 +216,7 @@ class GNPlan:
         self.n_kp = lin["r_proj"].shape[0] // (T * L) if T * L else 0
         m = T * max(L - 1, 0)
         self.m = m
-
-        def e(*shape, dtype=torch.float64):
-            return torch.empty(shape, dtype=dtype, device=dev)
-
+        e = _empty(dev)
         self.out = {"delta": e(T * L, 12), "info": e(T, dtype=torch.int32)}
         if blocks:
             self.out.update(D=e(T * L, 12, 12), E=e(max(m, 1), 12, 12), g=e(T * L, 12))
@@ -207,25 +226,13 @@ class GNPlan:
 
     def launch(self) -> None:
         """One pa_trajectory_gn_step on the device's current stream."""
-        lin, out, p = self.lin, self.out, _lib.ptr
+        lin, out, p, pr = self.lin, self.out, _lib.ptr, self.prior
         with torch.cuda.device(self.dev):
-            fac = (self.T, self.L, self.n_kp, p(lin["r_proj"]), p(lin["j_proj"]), p(lin.get("status")),
-                   p(lin["r_dyn"]), p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]),
-                   p(lin["r_cv"]), p(lin["j_cv0"]), p(lin["j_cv1"]))
-            tail = (self.lam, p(out.get("D")), p(out.get("E")), p(out.get("g")), p(out["delta"]), p(out["info"]),
-                    p(self.ws), self.ws.numel())
-            args = fac + tail
-            if lin.get("r_cw") is not None:  # the factor on the angular velocity travels in `lin`
-                pr = self.prior
-                _lib.check(_lib.lib().pa_trajectory_gn_step_cw(
-                    *fac, p(lin["r_cw"]), p(lin["isig_cw"]), *tail, p(pr.info) if pr else None,
-                    p(pr.grad) if pr else None, _lib.stream_of(self.dev)), "pa_trajectory_gn_step_cw")
-            elif self.prior is None:
-                _lib.check(_lib.lib().pa_trajectory_gn_step(*args, _lib.stream_of(self.dev)), "pa_trajectory_gn_step")
-            else:
-                _lib.check(_lib.lib().pa_trajectory_gn_step_prior(*args, p(self.prior.info), p(self.prior.grad),
-                                                                  _lib.stream_of(self.dev)),
-                           "pa_trajectory_gn_step_prior")
+            _lib.check(_lib.lib().pa_trajectory_gn_step_cw(
+                *_factor_args(lin, self.T, self.L, self.n_kp), p(lin.get("r_cw")), p(lin.get("isig_cw")), self.lam,
+                p(out.get("D")), p(out.get("E")), p(out.get("g")), p(out["delta"]), p(out["info"]), p(self.ws),
+                self.ws.numel(), p(pr.info) if pr else None, p(pr.grad) if pr else None, _lib.stream_of(self.dev)),
+                _entry("pa_trajectory_gn_step", lin, pr))
 
 
 def gn_step(lin: dict, *, T: int, L: int, lam: float = 0.0) -> dict:
@@ -267,10 +274,7 @@ class MarginalsPlan:
         dev = lin["r_proj"].device
         self.T, self.L, self.lam, self.lin, self.dev, self.prior = T, L, float(lam), lin, dev, prior
         self.n_kp = lin["r_proj"].shape[0] // (T * L) if T * L else 0
-
-        def e(*shape, dtype=torch.float64):
-            return torch.empty(shape, dtype=dtype, device=dev)
-
+        e = _empty(dev)
         self.out = {"info": e(T, dtype=torch.int32)}
         if full:
             self.out["cov"] = e(T * L, 12, 12)
@@ -283,26 +287,13 @@ class MarginalsPlan:
 
     def launch(self) -> None:
         """One pa_trajectory_marginals on the device's current stream."""
-        lin, out, p = self.lin, self.out, _lib.ptr
+        lin, out, p, pr = self.lin, self.out, _lib.ptr, self.prior
         with torch.cuda.device(self.dev):
-            fac = (self.T, self.L, self.n_kp, p(lin["r_proj"]), p(lin["j_proj"]), p(lin.get("status")),
-                   p(lin["r_dyn"]), p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]),
-                   p(lin["r_cv"]), p(lin["j_cv0"]), p(lin["j_cv1"]))
-            tail = (self.lam, p(out.get("cov")), p(out.get("cross")), p(out.get("cov_newest")), p(out["info"]),
-                    p(self.ws), self.ws.numel())
-            args = fac + tail
-            if lin.get("r_cw") is not None:  # the factor on the angular velocity travels in `lin`
-                pr = self.prior
-                _lib.check(_lib.lib().pa_trajectory_marginals_cw(
-                    *fac, p(lin["r_cw"]), p(lin["isig_cw"]), *tail, p(pr.info) if pr else None,
-                    p(pr.grad) if pr else None, _lib.stream_of(self.dev)), "pa_trajectory_marginals_cw")
-            elif self.prior is None:
-                _lib.check(_lib.lib().pa_trajectory_marginals(*args, _lib.stream_of(self.dev)),
-                           "pa_trajectory_marginals")
-            else:
-                _lib.check(_lib.lib().pa_trajectory_marginals_prior(*args, p(self.prior.info), p(self.prior.grad),
-                                                                    _lib.stream_of(self.dev)),
-                           "pa_trajectory_marginals_prior")
+            _lib.check(_lib.lib().pa_trajectory_marginals_cw(
+                *_factor_args(lin, self.T, self.L, self.n_kp), p(lin.get("r_cw")), p(lin.get("isig_cw")), self.lam,
+                p(out.get("cov")), p(out.get("cross")), p(out.get("cov_newest")), p(out["info"]), p(self.ws),
+                self.ws.numel(), p(pr.info) if pr else None, p(pr.grad) if pr else None, _lib.stream_of(self.dev)),
+                _entry("pa_trajectory_marginals", lin, pr))
 
 
 def marginals(lin: dict, *, T: int, L: int, lam: float, cross: bool = False) -> dict:
@@ -381,17 +372,12 @@ class PriorPlan:
         p, c, n = _lib.ptr, self.cur, self.nxt
         if n_kp is None:
             n_kp = lin["r_proj"].shape[0] // (self.T * self.L) if self.T * self.L and lin.get("r_proj") is not None else 0
-        fac = (self.T, self.L, n_kp, p(lin.get("r_proj")), p(lin.get("j_proj")), p(lin.get("status")), p(lin["r_dyn"]),
-               p(lin["j_dyn0"]), p(lin["j_dyn1"]), p(lin["j_dyn2"]), p(lin["j_dyn3"]), p(lin["r_cv"]),
-               p(lin["j_cv0"]), p(lin["j_cv1"]), p(c["info"]), p(self.grad))
-        tail = (float(lam), p(delta), p(gn_info), p(nvalid), p(pose), p(angvel), p(vel), p(n["info"]), p(n["eta"]),
-                p(n["xbar_pose"]), p(n["xbar_angvel"]), p(n["xbar_vel"]), p(self.minfo), _lib.stream_of(self.dev))
         with torch.cuda.device(self.dev):
-            if lin.get("r_cw") is not None:  # the factor on the angular velocity travels in `lin`
-                _lib.check(_lib.lib().pa_window_marginalize_cw(*fac, p(lin["r_cw"]), p(lin["isig_cw"]), *tail),
-                           "pa_window_marginalize_cw")
-            else:
-                _lib.check(_lib.lib().pa_window_marginalize(*fac, *tail), "pa_window_marginalize")
+            _lib.check(_lib.lib().pa_window_marginalize_cw(
+                *_factor_args(lin, self.T, self.L, n_kp), p(c["info"]), p(self.grad), p(lin.get("r_cw")),
+                p(lin.get("isig_cw")), float(lam), p(delta), p(gn_info), p(nvalid), p(pose), p(angvel), p(vel),
+                p(n["info"]), p(n["eta"]), p(n["xbar_pose"]), p(n["xbar_angvel"]), p(n["xbar_vel"]), p(self.minfo),
+                _lib.stream_of(self.dev)), _entry("pa_window_marginalize", lin, None))
 
     def advance(self) -> None:
         """The next prior becomes the current one: one device copy on the current stream (capturable;
@@ -438,10 +424,7 @@ class LMPlan:
         self.prior = prior
         if prior is not None and (prior.T, prior.L) != (T, L):
             raise ValueError(f"LMPlan: the prior is for T {prior.T}, L {prior.L}, the solve for T {T}, L {L}")
-
-        def e(*shape, dtype=torch.float64):
-            return torch.empty(shape, dtype=dtype, device=dev)
-
+        e = _empty(dev)
         self.out = {"cost0": e(T), "cost": e(T), "lambda": e(T), "iters": e(T, dtype=torch.int32),
                     "status": e(T, dtype=torch.int32), "cost_hist": e(T, max(self.max_iters, 0) + 1)}
         size = _lib.lib().pa_trajectory_lm_workspace if prior is None else _lib.lib().pa_trajectory_lm_prior_workspace
@@ -457,24 +440,13 @@ class LMPlan:
     def launch(self) -> None:
         """One pa_trajectory_lm_solve on the device's current stream."""
         o, p = self.out, _lib.ptr
+        pr = None if self.prior is None else C.byref(self._prior_struct())
+        what = f"pa_{'window' if self.newest_pending else 'trajectory'}_lm_{'' if pr is None else 'prior_'}solve"
         with torch.cuda.device(self.dev):
-            tail = (p(o["cost0"]), p(o["cost"]), p(o["iters"]), p(o["status"]), p(o["lambda"]), p(o["cost_hist"]),
-                    p(self.ws), self.ws.numel(), _lib.stream_of(self.dev))
-            if self.prior is not None:
-                pr = self._prior_struct()
-                if self.newest_pending:
-                    _lib.check(_lib.lib().pa_window_lm_prior_solve(C.byref(self.args), C.byref(self.params), 1,
-                                                                   C.byref(pr), *tail), "pa_window_lm_prior_solve")
-                else:
-                    _lib.check(_lib.lib().pa_trajectory_lm_prior_solve(C.byref(self.args), C.byref(self.params),
-                                                                       C.byref(pr), *tail),
-                               "pa_trajectory_lm_prior_solve")
-            elif self.newest_pending:
-                _lib.check(_lib.lib().pa_window_lm_solve(C.byref(self.args), C.byref(self.params), 1, *tail),
-                           "pa_window_lm_solve")
-            else:
-                _lib.check(_lib.lib().pa_trajectory_lm_solve(C.byref(self.args), C.byref(self.params), *tail),
-                           "pa_trajectory_lm_solve")
+            _lib.check(_lib.lib().pa_window_lm_prior_solve(
+                C.byref(self.args), C.byref(self.params), int(self.newest_pending), pr, p(o["cost0"]), p(o["cost"]),
+                p(o["iters"]), p(o["status"]), p(o["lambda"]), p(o["cost_hist"]), p(self.ws), self.ws.numel(),
+                _lib.stream_of(self.dev)), what)
 
 
 def lm_solve(y: torch.Tensor, poses, vels, angvels, corners, K, *, T: int, L: int, dt: float, proj_sigmas, dyn_sigmas,
@@ -538,13 +510,13 @@ def window_advance(y_new: torch.Tensor, win: dict, *, dt: float, vel_frame: str 
                 T, L, ny // 2, y_new.data_ptr(), win["y"].data_ptr(), win["pose"].data_ptr(),
                 win["angvel"].data_ptr(), win["vel"].data_ptr(), _lib.ptr(nvalid), _lib.ptr(win.get("dt")),
                 _lib.ptr(win.get("mask")), _lib.ptr(dt_new), _lib.ptr(mask_new), float(dt),
-                _lib.VEL_WORLD if vel_frame == "world" else _lib.VEL_BODY, _lib.stream_of(dev)), "pa_window_advance_t")
+                _vel_code(vel_frame), _lib.stream_of(dev)), "pa_window_advance_t")
         return
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().pa_window_advance_n(
             T, L, ny // 2, y_new.data_ptr(), win["y"].data_ptr(), win["pose"].data_ptr(), win["angvel"].data_ptr(),
-            win["vel"].data_ptr(), _lib.ptr(nvalid), float(dt),
-            _lib.VEL_WORLD if vel_frame == "world" else _lib.VEL_BODY, _lib.stream_of(dev)), "pa_window_advance")
+            win["vel"].data_ptr(), _lib.ptr(nvalid), float(dt), _vel_code(vel_frame),
+            _lib.stream_of(dev)), "pa_window_advance")
 
 
 TICK_MAX_L = 24  # pa_window_pose_tick: L <= 24 (the cyclic-reduction GN step), T <= the CU count
@@ -624,12 +596,6 @@ def window_retract(win: dict, delta: torch.Tensor, info: torch.Tensor | None = N
                                                        win["angvel"].data_ptr(), win["vel"].data_ptr(),
                                                        _lib.ptr(newest), _lib.stream_of(dev)),
                    "pa_window_retract")
-
-
-def _vel_code(vel_frame: str) -> int:
-    if vel_frame not in ("world", "body"):
-        raise AssertionError("vel_frame must be 'world' or 'body'.")  # factors.py:41
-    return _lib.VEL_WORLD if vel_frame == "world" else _lib.VEL_BODY
 
 
 class PredictPlan:
