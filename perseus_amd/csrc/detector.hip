@@ -963,6 +963,18 @@ int pa_detector_create(const float* weights, size_t nbytes, int in_ch, int n_kp,
   PA_CHECK(in_ch >= 1 && in_ch <= 4, "in_ch %d not in [1,4]", in_ch);
   PA_CHECK(n_kp >= 1 && n_kp <= 16, "n_kp %d not in [1,16]", n_kp);
   PA_CHECK(nbytes % 4 == 0, "nbytes %zu not a multiple of 4", nbytes);
+  // the blob's size for this shape, before the GPU is touched (build() walks the same layout):
+  // per conv the weights and 4 BN vectors, then the fc
+  size_t want = (size_t)64 * in_ch * 49 + 4 * 64;
+  for (int li = 0, cin = 64; li < 4; ++li) {
+    const size_t cout = (size_t)64 << li;
+    want += cout * cin * 9 + 3 * cout * cout * 9 + 4 * 4 * cout;
+    if (li > 0) want += cout * cin + 4 * cout;
+    cin = (int)cout;
+  }
+  want += (size_t)2 * n_kp * 512 + 2 * n_kp;
+  PA_CHECK(nbytes == 4 * want, "weight blob size mismatch: %zu bytes for in_ch=%d n_kp=%d (that shape has %zu)", nbytes,
+           in_ch, n_kp, 4 * want);
   pa_detector* d = new pa_detector();
   d->in_ch = in_ch;
   d->n_kp = n_kp;

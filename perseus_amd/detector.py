@@ -16,6 +16,8 @@ GPU, run there, and the result copied back to the input's device.
 
 Differences from the reference (documented in DESIGN.md): inference only (no
 autograd, `train()` mode is not supported), only 256x256 inputs, num_channels 1-4.
+The suite runs (num_channels, n_keypoints) = (3, 8), (4, 8), (1, 1), (2, 16), (3, 5), (4, 13) and
+n_keypoints 1-16 at 3 channels (tests/test_detector_shapes_gpu.py); the library refuses other counts.
 """
 
 from __future__ import annotations

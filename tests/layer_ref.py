@@ -46,7 +46,8 @@ Q_FACTOR = 4.0
 # and the stored result in the mode's formats, f32 conv2d / mean + linear between) on the f64 oracle's
 # own activations of synthetic_frames(6, 3), 4-channel model seed 0 and 3-channel model seed 2, per mode
 # and launch shape (ks, stride, Cin, Cout, residual, head); a max pool behind the conv does not change
-# the key.  Measured with measure_q_cpu() (python tests/layer_ref.py prints this table).  fp16's rows sit at 1: the storage rounding alone is
+# the key.  The 1- and 2-channel stems and the heads of another width than 16: from the stem and the head
+# of SHAPE_MODELS (below) on the first in_ch channels of the same frames.  Measured with measure_q_cpu() (python tests/layer_ref.py prints this table).  fp16's rows sit at 1: the storage rounding alone is
 # up to half an fp16 ulp = q 1.  The GPU's q is held to Q_FACTOR x these.
 Q_CPU = {
     "fp16": {
@@ -67,6 +68,12 @@ Q_CPU = {
         (3, 1, 512, 512, False, False): 0.985,
         (1, 1, 512, 16, False, True): 1.324,
         (7, 2, 3, 64, False, False): 0.998,
+        (7, 2, 1, 64, False, False): 0.997,
+        (1, 1, 512, 2, False, True): 0.794,
+        (7, 2, 2, 64, False, False): 0.997,
+        (1, 1, 512, 32, False, True): 1.398,
+        (1, 1, 512, 10, False, True): 1.296,
+        (1, 1, 512, 26, False, True): 1.207,
     },
     "fp32": {
         (7, 2, 4, 64, False, False): 2.558,
@@ -86,6 +93,12 @@ Q_CPU = {
         (3, 1, 512, 512, False, False): 0.623,
         (1, 1, 512, 16, False, True): 1.792,
         (7, 2, 3, 64, False, False): 3.158,
+        (7, 2, 1, 64, False, False): 2.457,
+        (1, 1, 512, 2, False, True): 0.465,
+        (7, 2, 2, 64, False, False): 2.506,
+        (1, 1, 512, 32, False, True): 1.797,
+        (1, 1, 512, 10, False, True): 1.042,
+        (1, 1, 512, 26, False, True): 1.088,
     },
     "fp16x3": {
         (7, 2, 4, 64, False, False): 1.930,
@@ -105,6 +118,12 @@ Q_CPU = {
         (3, 1, 512, 512, False, False): 0.539,
         (1, 1, 512, 16, False, True): 1.932,
         (7, 2, 3, 64, False, False): 1.709,
+        (7, 2, 1, 64, False, False): 1.380,
+        (1, 1, 512, 2, False, True): 0.866,
+        (7, 2, 2, 64, False, False): 1.532,
+        (1, 1, 512, 32, False, True): 1.394,
+        (1, 1, 512, 10, False, True): 1.932,
+        (1, 1, 512, 26, False, True): 1.813,
     },
 }
 
@@ -276,7 +295,11 @@ def check(gpu, r):
 
 
 def q_cap(mode, key):
-    """The largest q a GPU launch of this shape may show: Q_FACTOR x the CPU f32 yardstick."""
+    """The largest q a GPU launch of this shape may show: Q_FACTOR x the CPU f32 yardstick.  A head
+    of another width than 16 has as few as 2 outputs per frame, a thin sample of q: its yardstick is
+    the mode's largest head row over all measured widths (K = 64 + 512 whatever the width)."""
+    if key[5] and key[3] != 16:
+        return Q_FACTOR * max(v for k, v in Q_CPU[mode].items() if k[5])
     return Q_FACTOR * Q_CPU[mode][key]
 
 
@@ -381,7 +404,7 @@ def oracle_refs(l, state, mode):
     x = stem_input(l["x"], mode) if l["name"] == "stem" else store(l["x"], mode)
     if l["head"]:
         return ({"out": head_launch(mode, x, state["resnet.fc.weight"], state["resnet.fc.bias"])},
-                {"out": shape_key(1, 1, x.shape[1], 16, head=True)})
+                {"out": shape_key(1, 1, x.shape[1], np.asarray(state["resnet.fc.weight"]).shape[0], head=True)})
     res = None if l["res"] is None else store(l["res"], mode)
     w, b = fold(state, l["keys"], mode)
     refs = {"out": conv_launch(mode, x, w, b, res, l["relu"], l["stride"], l["maxpool"])}
@@ -393,24 +416,42 @@ def oracle_refs(l, state, mode):
     return refs, keys
 
 
+# (seed, in_ch, n_kp) of the models whose stem and head alone are measured: the channel and keypoint
+# counts between the library's limits (tests/test_detector_shapes_gpu.py runs them on the GPU)
+SHAPE_MODELS = ((0, 1, 1), (1, 2, 16), (2, 3, 5), (3, 4, 13))
+
+
 def measure_q_cpu(B=3):
     """{mode: {shape key: largest per-frame q of cpu_f32}} over every launch of the oracle's forward
-    (the 4-channel model, seed 0, and the 3-channel one, seed 2, on synthetic_frames(6, B)); also
-    prints the largest |err| / bound of cpu_f32 per mode."""
+    (the 4-channel model, seed 0, and the 3-channel one, seed 2, on synthetic_frames(6, B)), then the
+    stem and the head of SHAPE_MODELS for the keys those two do not have (the 1- and 2-channel stems,
+    the heads of 2, 10, 26 and 32 outputs; a key of the first two models keeps their row); also prints
+    the largest |err| / bound of cpu_f32 per mode."""
     from perseus_amd import synth
 
     table = {m: {} for m in MODES}
     worst = {m: 0.0 for m in MODES}
-    for seed, in_ch in ((0, 4), (2, 3)):
-        state = synth.synthetic_state_dict(seed, in_ch)
+    base = set()
+    for seed, in_ch, n_kp in ((0, 4, 8), (2, 3, 8)) + SHAPE_MODELS:
+        extra = (seed, in_ch, n_kp) in SHAPE_MODELS
+        state = synth.synthetic_state_dict(seed, in_ch, n_kp)
         x = synth.synthetic_frames(6, B)[:, :in_ch].copy()
         for l in oracle_launches(state, x):
+            if extra and not (l["name"] == "stem" or l["head"]):
+                continue
             for mode in MODES:
                 refs, keys = oracle_refs(l, state, mode)
                 got = cpu_f32(l, state, mode)
                 for o, r in refs.items():
                     ok, ratio, _, q = check(got[o], r)
                     worst[mode] = max(worst[mode], ratio)
+                    if extra:
+                        print(f"model {(seed, in_ch, n_kp)} {mode} {l['name']}: |err|/bound {ratio:.3f} q "
+                              f"{float(q.max()):.3f} non-zero {float((got[o] != 0).double().mean()):.2f}")
+                        if keys[o] in base:
+                            continue
+                    else:
+                        base.add(keys[o])
                     table[mode][keys[o]] = max(table[mode].get(keys[o], 0.0), float(q.max()))
     print("largest |err| / bound of the CPU f32 launches:", worst)
     return table

@@ -54,6 +54,24 @@ def test_bad_arguments_fail_loudly_without_touching_the_gpu():
                                       None), "dyn")
 
 
+@pytest.mark.parametrize("in_ch,n_kp,number", [(0, 8, b"in_ch 0"), (5, 8, b"in_ch 5"), (4, 0, b"n_kp 0"),
+                                               (4, 17, b"n_kp 17"), (3, 8, b"in_ch=3"), (4, 9, b"n_kp=9")])
+def test_detector_create_rejects_shapes_outside_its_range(in_ch, n_kp, number):
+    """pa_detector_create takes 1 .. 4 channels and 1 .. 16 keypoints, and a weight blob of exactly
+    that shape's size: a (4, 8) blob offered as another shape is refused before the GPU is touched,
+    with PA_EINVAL and the offending number in pa_last_error."""
+    from perseus_amd import synth
+
+    L = _lib.lib()
+    blob = synth.weight_blob(synth.synthetic_state_dict(0, 4, 8), 4, 8)
+    h = ctypes.c_void_p(1)
+    rc = L.pa_detector_create(blob.ctypes.data, blob.nbytes, in_ch, n_kp, 256, 256, ctypes.byref(h))
+    assert rc == -1 and h.value is None, (rc, h.value, L.pa_last_error())  # PA_EINVAL, no handle
+    assert number in L.pa_last_error(), L.pa_last_error()
+    if (in_ch, n_kp) in ((3, 8), (4, 9)):
+        assert str(blob.nbytes).encode() in L.pa_last_error()
+
+
 def test_gfx950_code_object_present():
     data = open(build.LIB, "rb").read()
     assert b"gfx950" in data
